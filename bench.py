@@ -17,7 +17,15 @@ rank solves its own 65536-instance shard).  ``--global-batch G`` instead
 splits a fixed global batch over the ranks (strong scaling; configs[3] is
 ``--N 20 --straight --mu-sweep --global-batch 262144``).
 
-Launch:  python bench.py [--gpus 1] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K steps and prints the line.
+``--full`` adds what takes runs of its own: the CPU baseline (the oracle's C
+port on this host) and the parity of the GPU's u* against it
+(``cpu_baseline``, ``parity_sample``; null without ``--full``).
+``--dump-outputs DIR`` writes what the last timed step returned (u, x, obj,
+status, iters, active; a fixed sample of instances, their ids in index.npy)
+as DIR/<name>.npy, so that two builds can be compared output for output.
+
+Launch:  python bench.py [--gpus 1] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
          python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 Rank 0 prints ONE JSON line.
 """
@@ -129,9 +137,15 @@ def parse():
                          'exchange): brings the clock to its steady state, which the first ~15 launches '
                          'otherwise ramp through (DESIGN.md 5); 0 disables.  Changes neither --steps, '
                          '--warmup nor the timed region')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline figure does not need: the CPU baseline and the '
+                         'GPU-vs-port parity sample (cpu_baseline, parity_sample)')
     ap.add_argument('--cpu-seconds', type=float, default=12.0,
-                    help='budget of the bounded CPU-baseline sample, split over its two legs '
-                         '(all cores, then one core); 0 disables')
+                    help='with --full: budget of the bounded CPU-baseline sample, split over its two '
+                         'legs (all cores, then one core); 0 disables')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step as DIR/<name>.npy (float64; a fixed '
+                         'sample of instances when the batch exceeds DUMP_BYTES)')
     return ap.parse_args()
 
 
@@ -204,6 +218,27 @@ def cpu_baseline(args, inst, gpu_u, gpu_status, budget_s):
               'note': 'max_abs_du over instances both solve; status_mismatch keys are '
                       '"gpu_status,port_status" (0 solved, 1 max_iter, 2 primal_infeasible, 3 numerical)'}
     return base, parity
+
+
+DUMP_BYTES = 60_000_000   # of --dump-outputs, all arrays together
+
+
+def dump_outputs(path, out, rank, world):
+    """What a caller of the timed path receives from its last step, as float64
+    .npy files: every instance, or a fixed seeded sample of them (index.npy
+    holds their positions in this rank's shard) within DUMP_BYTES."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    B = out['obj'].shape[0]
+    per = 8 * (1 + sum(v[0].numel() for v in out.values()))
+    idx = np.arange(B)
+    if per * B > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(B, DUMP_BYTES // per, replace=False))
+    sfx = f'_rank{rank}' if world > 1 else ''
+    np.save(os.path.join(path, f'index{sfx}.npy'), idx.astype(np.float64))
+    sel = torch.from_numpy(idx).to(out['obj'].device)
+    for k, v in out.items():
+        np.save(os.path.join(path, f'{k}{sfx}.npy'), v.index_select(0, sel).cpu().numpy().astype(np.float64))
 
 
 def main():
@@ -330,8 +365,11 @@ def main():
         dist_info = {'world_size': dist.get_world_size(), 'backend': backend,
                      'exchange_calls': ex.calls, 'exchange_bytes_per_rank_per_step': ex.slot}
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last[0], rank, world)
+
     base = parity = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         base, parity = cpu_baseline(args, inst, out['u'].cpu().numpy(), st, args.cpu_seconds)
 
     if rank == 0:

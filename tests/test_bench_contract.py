@@ -36,7 +36,7 @@ def test_workload_labels_name_the_baseline_configs():
 @pytest.mark.gpu
 def test_bench_line_contract():
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--prewarm-ms', '100',
-           '--cpu-seconds', '1', '--batch', '4096']
+           '--full', '--cpu-seconds', '1', '--batch', '4096']
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=110, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
@@ -61,3 +61,53 @@ def test_bench_line_contract():
     assert d['prewarm_ms'] >= 100 and d['prewarm_steps'] > 0
     p = d['parity_sample']
     assert p['instances'] > 0 and p['max_abs_du_vs_port'] <= 1e-6 and p['status_mismatch_total'] == 0
+
+
+@pytest.mark.gpu
+def test_plain_run_skips_the_baseline_and_dumps_its_outputs(tmp_path):
+    """Without --full: no CPU baseline, no parity sample.  --dump-outputs writes the last
+    step's outputs as float64 .npy, the same from run to run of one build (seeded inputs)."""
+    import numpy as np
+    B, N = 1024, 10
+    dumps = []
+    for name in ('a', 'b'):
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
+               '--prewarm-ms', '0', '--batch', str(B), '--dump-outputs', str(tmp_path / name)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=110, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
+        assert len(lines) == 1, out.stdout
+        d = json.loads(lines[0])
+        assert d['cpu_baseline'] is None and d['parity_sample'] is None
+        assert d['steps'] == 2 and d['metric'] == bench.METRIC and d['dtype'] == 'f64'
+        assert abs(d['value'] - B / (d['ms_per_step'] * 1e-3)) <= 1e-6 * d['value']
+        dumps.append({f[:-4]: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))})
+    a, b = dumps
+    shapes = {'u': (B, N, 6), 'x': (B, N + 1, 12), 'obj': (B,), 'status': (B,), 'iters': (B,), 'active': (B,),
+              'index': (B,)}
+    assert {k: v.shape for k, v in a.items()} == shapes
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert np.array_equal(a['index'], np.arange(B)) and (a['status'] == 0).mean() > 0.9
+    for k in shapes:
+        assert np.array_equal(a[k], b[k]), k
+
+
+def test_dump_sample_is_fixed_and_within_budget(tmp_path, monkeypatch):
+    """A batch above the byte budget is dumped as a seeded sample of instances (CPU tensors here)."""
+    import numpy as np
+    torch = pytest.importorskip('torch')
+    assert bench.DUMP_BYTES + 7 * 128 <= 64_000_000   # the budget, plus the .npy headers
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 100_000)
+    B = 1000   # 62 doubles each: 496 kB, five times the budget
+    out = dict(u=torch.arange(B * 60, dtype=torch.float64).reshape(B, 10, 6), obj=torch.arange(B, dtype=torch.float64))
+    for name in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / name), out, 0, 1)
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == ['index.npy', 'obj.npy', 'u.npy']
+    assert sum(os.path.getsize(tmp_path / 'a' / f) - 128 for f in files) <= 100_000
+    idx = np.load(tmp_path / 'a' / 'index.npy').astype(np.int64)
+    assert len(idx) == 100_000 // (8 * 62) and (np.diff(idx) > 0).all() and idx[-1] < B
+    assert np.array_equal(np.load(tmp_path / 'a' / 'obj.npy'), idx.astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / 'a' / 'u.npy')[:, 0, 0], 60.0 * idx)
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)), f

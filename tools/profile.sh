@@ -22,7 +22,7 @@ for cfg in $CFGS; do
   mkdir -p $O
   A=${ARGS[$cfg]}
   cd $R
-  timeout -k 10 300 python bench.py $A > $O/bench.json 2> $O/bench.err || { echo "$cfg bench failed"; exit 1; }
+  timeout -k 10 300 python bench.py $A --full > $O/bench.json 2> $O/bench.err || { echo "$cfg bench failed"; exit 1; }
   echo "$cfg bench ok"
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/trace -o run -- \
