@@ -913,6 +913,37 @@ int hmpc_convert_batch(hmpc_ctx* c, int64_t B, const double* X, double* x, void*
   return HMPC_OK;
 }
 
+int hmpc_kkt_batch(hmpc_ctx* c, int64_t B, const double* x_in, const double* x_lin, const double* x_ref,
+                   const double* pf, const double* C, const double* mu, const double* u, const double* x,
+                   double act_tol, double* nu, double* lam, double* cert, int32_t* flags, void* stream) {
+  if (!c) return HMPC_ERR_ARG;
+  if (c->variant == HMPC_VARIANT_CAS || c->N > hmpc::kKktNmax) {
+    c->err = "hmpc_kkt_batch serves the 3f and 2f variants up to N = 64";
+    return HMPC_ERR_UNSUPPORTED;
+  }
+  if (B < 0 || !(act_tol >= 0.0)) { c->err = "B < 0 or act_tol < 0"; return HMPC_ERR_ARG; }
+  if (B == 0) return HMPC_OK;
+  if (B > 0x7fffffffLL) { c->err = "B exceeds the grid limit"; return HMPC_ERR_ARG; }
+  if (!x_in || !x_lin || !x_ref || !pf || !C || !u || !x || !cert) {
+    c->err = "null input/output pointer";
+    return HMPC_ERR_ARG;
+  }
+  HMPC_HIP(c, hipSetDevice(c->device));
+  hmpc::KktArgs a;
+  a.x_in = x_in; a.x_lin = x_lin; a.x_ref = x_ref; a.pf = pf; a.C = C; a.mu = mu; a.u = u; a.x = x;
+  a.nu = nu; a.lam = lam; a.cert = cert; a.flags = flags;
+  a.B = B; a.N = c->N;
+  a.dt = c->t; a.m = c->m; a.g = c->g; a.mu_default = c->mu; a.act_tol = act_tol;
+  memcpy(a.Jinv, c->Jinv, sizeof(a.Jinv));
+  memcpy(a.rh, c->rh, sizeof(a.rh));
+  a.uref_aliased = c->uref_mode == HMPC_UREF_ALIASED ? 1 : 0;
+  int rc;
+  if ((rc = order_stream(c, (hipStream_t)stream)) != HMPC_OK) return rc;
+  hmpc::launch_kkt(c->variant, a, (hipStream_t)stream);
+  HMPC_HIP(c, hipGetLastError());
+  return mark_stream(c, (hipStream_t)stream);
+}
+
 int hmpc_plan_batch(hmpc_ctx* c, int64_t B, int N_run, int N_k, double dt, int curve, double t_p,
                     double phi_switch, double t_start, int step_adjustment, const double* x_in,
                     const double* xf, double* x_ref, double* pf_ref, double* C_map, void* stream) {

@@ -208,6 +208,30 @@ struct PlantArgs {
 };
 void launch_plant(const PlantArgs& a, hipStream_t s);
 void launch_convert(int64_t B, const double* X, double* x, hipStream_t s);
+// Multipliers and KKT certificate of a given primal point (hmpc_kkt.hip): one
+// wavefront per instance, 3f / 2f, 1 <= N <= kKktNmax.
+constexpr int kKktNmax = 64;
+struct KktArgs {
+  const double* x_in;    // [B,12]
+  const double* x_lin;   // [B,N+1,12]
+  const double* x_ref;   // [B,N,12]
+  const double* pf;      // [B,N,3]
+  const double* C;       // [B,N]
+  const double* mu;      // [B] or nullptr
+  const double* u;       // [B,N,6]   the primal point
+  const double* x;       // [B,N+1,12]
+  double* nu;            // [B,N] or nullptr
+  double* lam;           // [B,N,11] or nullptr
+  double* cert;          // [B,5]
+  int32_t* flags;        // [B] or nullptr
+  int64_t B;
+  int N;
+  double dt, m, g, mu_default, act_tol;
+  double Jinv[9];
+  double rh[3];
+  int uref_aliased;
+};
+void launch_kkt(int variant, const KktArgs& a, hipStream_t s);
 // the CasADi variant's kernel (hmpc_cas.hip): R slots of cas_ws_stride
 // doubles per resident workgroup in a.kws, instance counter a.work,
 // a.ric_groups workgroups

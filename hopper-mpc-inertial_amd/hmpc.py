@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get('HMPC_LIB', os.path.join(HERE, 'libhmpc.so'))
 
 HMPC_OK = 0
 ERRORS = {-1: 'HMPC_ERR_ARG', -2: 'HMPC_ERR_UNSUPPORTED', -3: 'HMPC_ERR_HIP', -4: 'HMPC_ERR_NOMEM'}
+KKT_SINGULAR = 1   # kkt_device flags: dependent active z rows (HMPC_KKT_SINGULAR)
 STATUS = {0: 'solved', 1: 'max_iter', 2: 'primal_infeasible', 3: 'numerical'}
 VARIANTS = {'3f': 3, '2f': 2, 'cas': 4, 3: 3, 2: 2, 4: 4}
 UREF = {'aliased': 0, 'per_stage': 1}
@@ -38,6 +39,7 @@ SIGNATURES = {
     'hmpc_destroy': (ctypes.c_int, [_VP]),
     'hmpc_solve_batch': (ctypes.c_int, [_VP, ctypes.c_int64] + [_VP] * 11 + [_VP]),
     'hmpc_solve_batch_stats': (ctypes.c_int, [_VP, ctypes.c_int64] + [_VP] * 12 + [_VP]),
+    'hmpc_kkt_batch': (ctypes.c_int, [_VP, ctypes.c_int64] + [_VP] * 8 + [ctypes.c_double] + [_VP] * 4 + [_VP]),
     'hmpc_set_refinement': (ctypes.c_int, [_VP, ctypes.c_int]),
     'hmpc_set_order': (ctypes.c_int, [_VP, ctypes.c_int]),
     'hmpc_solve_batch_host': (ctypes.c_int, [_VP, ctypes.c_int64] + [_VP] * 11),
@@ -250,6 +252,37 @@ class Context:
                                               _ptr(out.get('iters')), _ptr(out.get('active')),
                                               ctypes.c_void_p(s))
         self._check(rc, 'hmpc_solve_batch_stats')
+        return out
+
+    def kkt_device(self, x_in, x_lin, x_ref, pf, C, u, x, mu=None, act_tol=1e-8, out=None, stream=None):
+        """Multipliers and KKT certificate of the primal point (x, u)
+        (hmpc_kkt_batch): nu (B,N), lam (B,N,11), cert (B,5) = primal_eq,
+        primal_ineq, dual_neg, stationarity, complementarity, and flags (B,)
+        (KKT_SINGULAR).  Inputs as solve_device; async on `stream`."""
+        import torch
+        N = self.N
+        B = x_in.shape[0]
+        for t_, shp, nm in ((x_in, (B, 12), 'x_in'), (x_lin, (B, N + 1, 12), 'x_lin'),
+                            (x_ref, (B, N, 12), 'x_ref'), (pf, (B, N, 3), 'pf'), (C, (B, N), 'C'),
+                            (u, (B, N, 6), 'u'), (x, (B, N + 1, 12), 'x')):
+            _check_tensor(t_, shp, nm, self.device)
+        _check_tensor(mu, (B,), 'mu', self.device, optional=True)
+        if out is None:
+            dev = x_in.device
+            out = dict(nu=torch.empty((B, N), dtype=torch.float64, device=dev),
+                       lam=torch.empty((B, N, 11), dtype=torch.float64, device=dev),
+                       cert=torch.empty((B, 5), dtype=torch.float64, device=dev),
+                       flags=torch.empty(B, dtype=torch.int32, device=dev))
+        _check_tensor(out.get('nu'), (B, N), "out['nu']", self.device, optional=True)
+        _check_tensor(out.get('lam'), (B, N, 11), "out['lam']", self.device, optional=True)
+        _check_tensor(out.get('cert'), (B, 5), "out['cert']", self.device)
+        _check_tensor(out.get('flags'), (B,), "out['flags']", self.device, dtype='int32', optional=True)
+        s = stream if stream is not None else torch.cuda.current_stream(x_in.device).cuda_stream
+        rc = self._lib.hmpc_kkt_batch(self._h, B, _ptr(x_in), _ptr(x_lin), _ptr(x_ref), _ptr(pf), _ptr(C),
+                                      _ptr(mu), _ptr(u), _ptr(x), float(act_tol), _ptr(out.get('nu')),
+                                      _ptr(out.get('lam')), _ptr(out['cert']), _ptr(out.get('flags')),
+                                      ctypes.c_void_p(s))
+        self._check(rc, 'hmpc_kkt_batch')
         return out
 
     def mpcontrol_device(self, init, x_in, x_ref, pf, C, x_prev, mu=None, out=None, stream=None):

@@ -28,6 +28,9 @@
  *                           + gait_map (:174-180), one plan per robot
  *   hmpc_gait_batch      <- the Runner loop's gait_scheduler / gait_map calls
  *                           (src/robotrunner.py:92-101)
+ *   hmpc_kkt_batch       <- the duals problem.solve() leaves in cvxpy's
+ *                           dual_value / OSQP's y (src/mpc_cvx_euler_3f.py:156-157)
+ *                           for a given primal point, plus a KKT certificate
  *   hmpc_destroy         <- object lifetime
  *
  * Conventions: every array is row-major, contiguous, float64, batch-major
@@ -103,7 +106,8 @@ typedef struct hmpc_ctx hmpc_ctx;
    1.5.1 = hmpc_kernel_name / hmpc_active_capacity report the last solve's N = 60
            kernel (capacity 64 at small batches);
    1.5.2 = the cross-stream completion event is recorded at a stream switch,
-           not after every call (the last call's stream must stay valid) */
+           not after every call (the last call's stream must stay valid);
+           + hmpc_kkt_batch (an addition: the version number is unchanged) */
 int hmpc_version(void);
 
 /* Which horizons have a dedicated (one- or two-wavefront) kernel for
@@ -296,6 +300,39 @@ int hmpc_active_capacity(hmpc_ctx* ctx);
    convergence test failed.  Waits for the context's last solve.  No
    reference analogue: it reports where the GPU path spends its slow pass. */
 int hmpc_overflow_total(hmpc_ctx* ctx, int64_t* total);
+
+/* Lagrange multipliers and a KKT certificate of a primal point (x, u) of the
+   QP hmpc_solve_batch solves: what problem.solve() leaves in cvxpy's
+   dual_value / OSQP's y (src/mpc_cvx_euler_3f.py:156-157).  Inputs as
+   hmpc_solve_batch (device pointers); u [B,N,6] and x [B,N+1,12] are the point
+   to certify -- a solve's output at any precision, or a point from elsewhere.
+   A row is active when its slack is <= act_tol (1 + |bound|) (1e-8 is the
+   usual value).  Outputs, in the sign convention of OSQP's y:
+     nu   [B,N]     multiplier of x[k][2] >= 0.1, nu >= 0 (nu[0] = 0: that row
+                    sits on the fixed x[0]); may be NULL
+     lam  [B,N,11]  per stage (may be NULL):
+                    0-2   tau_x, tau_y, tau_z (> 0 at the upper bound, < 0 at the lower)
+                    3-6   fx - mu fz, -fx - mu fz, fy - mu fz, -fy - mu fz (>= 0)
+                    7     fz (> 0 at 206, < 0 at 0)
+                    8-10  the fixed fx, fy, fz (swing stages; 2f: fy), free sign
+                    unused slots are 0.  At a stance stage with fz = 0 the five
+                    force rows are dependent: the minimal nonnegative split is
+                    reported (friction rows take the positive and negative parts,
+                    fz >= 0 the rest)
+     cert [B,5]     primal_eq, primal_ineq, dual_neg, stationarity (scaled by
+                    1 + max|q|), complementarity: the certificate of a QP in
+                    OSQP form, l <= A z <= u
+     flags[B]       HMPC_KKT_SINGULAR when active z rows are dependent given
+                    the pinned inputs (their nu is then reported as 0); may be NULL
+   Serves the 3f and 2f variants for 1 <= N <= 64 (else HMPC_ERR_UNSUPPORTED).
+   Asynchronous, allocates nothing (can be captured into a HIP graph). */
+#define HMPC_KKT_SINGULAR 1
+int hmpc_kkt_batch(hmpc_ctx* ctx, int64_t B,
+                   const double* x_in, const double* x_lin, const double* x_ref,
+                   const double* pf, const double* C, const double* mu,
+                   const double* u, const double* x, double act_tol,
+                   double* nu, double* lam, double* cert, int32_t* flags,
+                   void* stream);
 
 /* Last HIP error string of this context ("" if none). */
 const char* hmpc_last_error(hmpc_ctx* ctx);
