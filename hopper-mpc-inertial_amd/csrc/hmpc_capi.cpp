@@ -944,6 +944,39 @@ int hmpc_kkt_batch(hmpc_ctx* c, int64_t B, const double* x_in, const double* x_l
   return mark_stream(c, (hipStream_t)stream);
 }
 
+int hmpc_sens_batch(hmpc_ctx* c, int64_t B, const double* x_in, const double* x_lin, const double* x_ref,
+                    const double* pf, const double* C, const double* mu, const double* u, const double* x,
+                    double act_tol, int n_stages, double* S, int32_t* flags, void* stream) {
+  if (!c) return HMPC_ERR_ARG;
+  if (c->variant == HMPC_VARIANT_CAS || c->N > hmpc::kSensNmax) {
+    c->err = "hmpc_sens_batch serves the 3f and 2f variants up to N = 64";
+    return HMPC_ERR_UNSUPPORTED;
+  }
+  if (B < 0 || !(act_tol >= 0.0)) { c->err = "B < 0 or act_tol < 0"; return HMPC_ERR_ARG; }
+  if (n_stages < 1 || n_stages > c->N) { c->err = "n_stages outside 1..N"; return HMPC_ERR_ARG; }
+  if (B == 0) return HMPC_OK;
+  if (B > 0x7fffffffLL) { c->err = "B exceeds the grid limit"; return HMPC_ERR_ARG; }
+  // x_in and x_ref do not enter the Jacobian (they move the optimum, not its
+  // slope); they are required so that the call reads like hmpc_solve_batch
+  if (!x_in || !x_lin || !x_ref || !pf || !C || !u || !x || !S) {
+    c->err = "null input/output pointer";
+    return HMPC_ERR_ARG;
+  }
+  HMPC_HIP(c, hipSetDevice(c->device));
+  hmpc::SensArgs a;
+  a.x_lin = x_lin; a.pf = pf; a.C = C; a.mu = mu; a.u = u; a.x = x;
+  a.S = S; a.flags = flags;
+  a.B = B; a.N = c->N; a.n_stages = n_stages;
+  a.dt = c->t; a.m = c->m; a.mu_default = c->mu; a.act_tol = act_tol;
+  memcpy(a.Jinv, c->Jinv, sizeof(a.Jinv));
+  memcpy(a.rh, c->rh, sizeof(a.rh));
+  int rc;
+  if ((rc = order_stream(c, (hipStream_t)stream)) != HMPC_OK) return rc;
+  hmpc::launch_sens(c->variant, a, (hipStream_t)stream);
+  HMPC_HIP(c, hipGetLastError());
+  return mark_stream(c, (hipStream_t)stream);
+}
+
 int hmpc_plan_batch(hmpc_ctx* c, int64_t B, int N_run, int N_k, double dt, int curve, double t_p,
                     double phi_switch, double t_start, int step_adjustment, const double* x_in,
                     const double* xf, double* x_ref, double* pf_ref, double* C_map, void* stream) {

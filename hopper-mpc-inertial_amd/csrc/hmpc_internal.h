@@ -232,6 +232,25 @@ struct KktArgs {
   int uref_aliased;
 };
 void launch_kkt(int variant, const KktArgs& a, hipStream_t s);
+// Sensitivity du*/dx_in at the active set of a given primal point
+// (hmpc_sens.hip): one wavefront per instance, 3f / 2f, 1 <= N <= kSensNmax.
+constexpr int kSensNmax = 64;
+struct SensArgs {
+  const double* x_lin;   // [B,N+1,12]
+  const double* pf;      // [B,N,3]
+  const double* C;       // [B,N]
+  const double* mu;      // [B] or nullptr
+  const double* u;       // [B,N,6]   the primal point
+  const double* x;       // [B,N+1,12]
+  double* S;             // [B,n_stages,6,12]
+  int32_t* flags;        // [B] or nullptr
+  int64_t B;
+  int N, n_stages;
+  double dt, m, mu_default, act_tol;
+  double Jinv[9];
+  double rh[3];
+};
+void launch_sens(int variant, const SensArgs& a, hipStream_t s);
 // the CasADi variant's kernel (hmpc_cas.hip): R slots of cas_ws_stride
 // doubles per resident workgroup in a.kws, instance counter a.work,
 // a.ric_groups workgroups

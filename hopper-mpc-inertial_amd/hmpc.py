@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get('HMPC_LIB', os.path.join(HERE, 'libhmpc.so'))
 HMPC_OK = 0
 ERRORS = {-1: 'HMPC_ERR_ARG', -2: 'HMPC_ERR_UNSUPPORTED', -3: 'HMPC_ERR_HIP', -4: 'HMPC_ERR_NOMEM'}
 KKT_SINGULAR = 1   # kkt_device flags: dependent active z rows (HMPC_KKT_SINGULAR)
+SENS_SINGULAR, SENS_ZROWS = 1, 2   # sens_device flags (HMPC_SENS_SINGULAR, HMPC_SENS_ZROWS)
 STATUS = {0: 'solved', 1: 'max_iter', 2: 'primal_infeasible', 3: 'numerical'}
 VARIANTS = {'3f': 3, '2f': 2, 'cas': 4, 3: 3, 2: 2, 4: 4}
 UREF = {'aliased': 0, 'per_stage': 1}
@@ -40,6 +41,8 @@ SIGNATURES = {
     'hmpc_solve_batch': (ctypes.c_int, [_VP, ctypes.c_int64] + [_VP] * 11 + [_VP]),
     'hmpc_solve_batch_stats': (ctypes.c_int, [_VP, ctypes.c_int64] + [_VP] * 12 + [_VP]),
     'hmpc_kkt_batch': (ctypes.c_int, [_VP, ctypes.c_int64] + [_VP] * 8 + [ctypes.c_double] + [_VP] * 4 + [_VP]),
+    'hmpc_sens_batch': (ctypes.c_int, [_VP, ctypes.c_int64] + [_VP] * 8 + [ctypes.c_double, ctypes.c_int]
+                        + [_VP] * 2 + [_VP]),
     'hmpc_set_refinement': (ctypes.c_int, [_VP, ctypes.c_int]),
     'hmpc_set_order': (ctypes.c_int, [_VP, ctypes.c_int]),
     'hmpc_solve_batch_host': (ctypes.c_int, [_VP, ctypes.c_int64] + [_VP] * 11),
@@ -283,6 +286,34 @@ class Context:
                                       _ptr(out.get('lam')), _ptr(out['cert']), _ptr(out.get('flags')),
                                       ctypes.c_void_p(s))
         self._check(rc, 'hmpc_kkt_batch')
+        return out
+
+    def sens_device(self, x_in, x_lin, x_ref, pf, C, u, x, mu=None, act_tol=1e-8, n_stages=None, out=None,
+                    stream=None):
+        """Jacobian of the solve at the primal point (x, u) (hmpc_sens_batch):
+        S (B,n_stages,6,12) = d u*_k / d x_in at the point's active set, and
+        flags (B,) (SENS_SINGULAR).  n_stages defaults to N; n_stages = 1 is
+        the feedback gain K_0.  Inputs as kkt_device; async on `stream`."""
+        import torch
+        N = self.N
+        B = x_in.shape[0]
+        ns = N if n_stages is None else int(n_stages)
+        for t_, shp, nm in ((x_in, (B, 12), 'x_in'), (x_lin, (B, N + 1, 12), 'x_lin'),
+                            (x_ref, (B, N, 12), 'x_ref'), (pf, (B, N, 3), 'pf'), (C, (B, N), 'C'),
+                            (u, (B, N, 6), 'u'), (x, (B, N + 1, 12), 'x')):
+            _check_tensor(t_, shp, nm, self.device)
+        _check_tensor(mu, (B,), 'mu', self.device, optional=True)
+        if out is None:
+            dev = x_in.device
+            out = dict(S=torch.empty((B, max(ns, 0), 6, 12), dtype=torch.float64, device=dev),
+                       flags=torch.empty(B, dtype=torch.int32, device=dev))
+        _check_tensor(out.get('S'), (B, max(ns, 0), 6, 12), "out['S']", self.device)
+        _check_tensor(out.get('flags'), (B,), "out['flags']", self.device, dtype='int32', optional=True)
+        s = stream if stream is not None else torch.cuda.current_stream(x_in.device).cuda_stream
+        rc = self._lib.hmpc_sens_batch(self._h, B, _ptr(x_in), _ptr(x_lin), _ptr(x_ref), _ptr(pf), _ptr(C),
+                                       _ptr(mu), _ptr(u), _ptr(x), float(act_tol), ns, _ptr(out['S']),
+                                       _ptr(out.get('flags')), ctypes.c_void_p(s))
+        self._check(rc, 'hmpc_sens_batch')
         return out
 
     def mpcontrol_device(self, init, x_in, x_ref, pf, C, x_prev, mu=None, out=None, stream=None):

@@ -31,6 +31,8 @@
  *   hmpc_kkt_batch       <- the duals problem.solve() leaves in cvxpy's
  *                           dual_value / OSQP's y (src/mpc_cvx_euler_3f.py:156-157)
  *                           for a given primal point, plus a KKT certificate
+ *   hmpc_sens_batch      <- no reference analogue: the Jacobian d u* / d x_in of that
+ *                           solve at its active set (feedback gain between solves)
  *   hmpc_destroy         <- object lifetime
  *
  * Conventions: every array is row-major, contiguous, float64, batch-major
@@ -107,7 +109,8 @@ typedef struct hmpc_ctx hmpc_ctx;
            kernel (capacity 64 at small batches);
    1.5.2 = the cross-stream completion event is recorded at a stream switch,
            not after every call (the last call's stream must stay valid);
-           + hmpc_kkt_batch (an addition: the version number is unchanged) */
+           + hmpc_kkt_batch, + hmpc_sens_batch (additions: the version number is
+           unchanged) */
 int hmpc_version(void);
 
 /* Which horizons have a dedicated (one- or two-wavefront) kernel for
@@ -333,6 +336,37 @@ int hmpc_kkt_batch(hmpc_ctx* ctx, int64_t B,
                    const double* u, const double* x, double act_tol,
                    double* nu, double* lam, double* cert, int32_t* flags,
                    void* stream);
+
+/* First-order sensitivity of the optimum to the measured state at a primal
+   point (x, u) of the QP hmpc_solve_batch solves:
+     S[b,k,c,i] = d u*_k[c] / d x_in[i],   k < n_stages
+   with x_lin, x_ref, pf, C and mu held fixed.  mpcontrol's own dependence of
+   x_lin[0] on x_in is NOT part of it: the derivative is that of one QP.  Inputs
+   as hmpc_kkt_batch (device pointers; x_in and x_ref do not enter the slope but
+   are required).  A row is active when its slack is <= act_tol (1 + |bound|),
+   the rule of hmpc_kkt_batch, and every active row is held as an equality
+   whether or not its multiplier is zero; a stance stage with fz = 0 pins all
+   three force components.  n_stages = 1 gives the feedback gain K_0 [B,6,12]
+   for u = u*_0 + K_0 (x - x_in) between solves.  Outputs:
+     S     [B,n_stages,6,12]   (also the call's only workspace: allocate exactly this)
+     flags [B]  HMPC_SENS_SINGULAR when an active z row is dependent given the
+                pinned inputs and was dropped (a z row at stage 1 always is).  The
+                z row of stage 0 sits on the fixed x[0] and is never held: with
+                x_in[2] at 0.1 it would contradict dx_0 = e_2, so S is the
+                derivative on the feasible side;
+                HMPC_SENS_ZROWS is reserved for a kernel that carries fewer z
+                rows than a horizon can hold (S would then be 0): this one
+                carries all N - 1 and never sets it.  May be NULL
+   Serves the 3f and 2f variants for 1 <= N <= 64 (else HMPC_ERR_UNSUPPORTED);
+   n_stages outside 1..N is HMPC_ERR_ARG.  Asynchronous, allocates nothing (can
+   be captured into a HIP graph). */
+#define HMPC_SENS_SINGULAR 1   /* a dependent active z row was dropped */
+#define HMPC_SENS_ZROWS    2   /* more active z rows than the kernel carries; S is 0 */
+int hmpc_sens_batch(hmpc_ctx* ctx, int64_t B,
+                    const double* x_in, const double* x_lin, const double* x_ref,
+                    const double* pf, const double* C, const double* mu,
+                    const double* u, const double* x, double act_tol,
+                    int n_stages, double* S, int32_t* flags, void* stream);
 
 /* Last HIP error string of this context ("" if none). */
 const char* hmpc_last_error(hmpc_ctx* ctx);
