@@ -251,6 +251,30 @@ struct SensArgs {
   double rh[3];
 };
 void launch_sens(int variant, const SensArgs& a, hipStream_t s);
+// Reverse-mode gradients of the solve at the same active set (hmpc_vjp.hip):
+// one wavefront per instance, 3f / 2f, 1 <= N <= kVjpNmax.
+constexpr int kVjpNmax = 64;
+struct VjpArgs {
+  const double* x_lin;   // [B,N+1,12]
+  const double* x_ref;   // [B,N,12]
+  const double* pf;      // [B,N,3]
+  const double* C;       // [B,N]
+  const double* mu;      // [B] or nullptr
+  const double* u;       // [B,N,6]   the primal point
+  const double* x;       // [B,N+1,12]
+  const double* g_u;     // [B,N,6] or nullptr (= 0)
+  const double* g_x;     // [B,N+1,12] or nullptr (= 0)
+  double* grad_x_in;     // [B,12] or nullptr
+  double* grad_x_ref;    // [B,N,12] or nullptr
+  double* grad_pf;       // [B,N,3] or nullptr
+  int32_t* flags;        // [B] or nullptr
+  int64_t B;
+  int N;
+  double dt, m, mu_default, act_tol;
+  double Jinv[9];
+  double rh[3];
+};
+void launch_vjp(int variant, const VjpArgs& a, hipStream_t s);
 // the CasADi variant's kernel (hmpc_cas.hip): R slots of cas_ws_stride
 // doubles per resident workgroup in a.kws, instance counter a.work,
 // a.ric_groups workgroups

@@ -20,6 +20,7 @@ HMPC_OK = 0
 ERRORS = {-1: 'HMPC_ERR_ARG', -2: 'HMPC_ERR_UNSUPPORTED', -3: 'HMPC_ERR_HIP', -4: 'HMPC_ERR_NOMEM'}
 KKT_SINGULAR = 1   # kkt_device flags: dependent active z rows (HMPC_KKT_SINGULAR)
 SENS_SINGULAR, SENS_ZROWS = 1, 2   # sens_device flags (HMPC_SENS_SINGULAR, HMPC_SENS_ZROWS)
+VJP_SINGULAR = 1   # vjp_device flags (HMPC_VJP_SINGULAR)
 STATUS = {0: 'solved', 1: 'max_iter', 2: 'primal_infeasible', 3: 'numerical'}
 VARIANTS = {'3f': 3, '2f': 2, 'cas': 4, 3: 3, 2: 2, 4: 4}
 UREF = {'aliased': 0, 'per_stage': 1}
@@ -43,6 +44,7 @@ SIGNATURES = {
     'hmpc_kkt_batch': (ctypes.c_int, [_VP, ctypes.c_int64] + [_VP] * 8 + [ctypes.c_double] + [_VP] * 4 + [_VP]),
     'hmpc_sens_batch': (ctypes.c_int, [_VP, ctypes.c_int64] + [_VP] * 8 + [ctypes.c_double, ctypes.c_int]
                         + [_VP] * 2 + [_VP]),
+    'hmpc_vjp_batch': (ctypes.c_int, [_VP, ctypes.c_int64] + [_VP] * 8 + [ctypes.c_double] + [_VP] * 6 + [_VP]),
     'hmpc_set_refinement': (ctypes.c_int, [_VP, ctypes.c_int]),
     'hmpc_set_order': (ctypes.c_int, [_VP, ctypes.c_int]),
     'hmpc_solve_batch_host': (ctypes.c_int, [_VP, ctypes.c_int64] + [_VP] * 11),
@@ -314,6 +316,39 @@ class Context:
                                        _ptr(mu), _ptr(u), _ptr(x), float(act_tol), ns, _ptr(out['S']),
                                        _ptr(out.get('flags')), ctypes.c_void_p(s))
         self._check(rc, 'hmpc_sens_batch')
+        return out
+
+    def vjp_device(self, x_in, x_lin, x_ref, pf, C, u, x, g_u=None, g_x=None, mu=None, act_tol=1e-8,
+                   want=('x_in', 'x_ref', 'pf'), out=None, stream=None):
+        """Reverse-mode gradients of the solve at the primal point (x, u)
+        (hmpc_vjp_batch): for the cotangents g_u (B,N,6) and g_x (B,N+1,12) of a
+        scalar loss (either may be None = 0), the gradients with respect to the
+        inputs named in `want`: x_in (B,12), x_ref (B,N,12), pf (B,N,3), and
+        flags (B,) (VJP_SINGULAR).  An input not in `want` is None in the result.
+        Inputs as sens_device; async on `stream`."""
+        import torch
+        N = self.N
+        B = x_in.shape[0]
+        for t_, shp, nm in ((x_in, (B, 12), 'x_in'), (x_lin, (B, N + 1, 12), 'x_lin'),
+                            (x_ref, (B, N, 12), 'x_ref'), (pf, (B, N, 3), 'pf'), (C, (B, N), 'C'),
+                            (u, (B, N, 6), 'u'), (x, (B, N + 1, 12), 'x')):
+            _check_tensor(t_, shp, nm, self.device)
+        for t_, shp, nm in ((mu, (B,), 'mu'), (g_u, (B, N, 6), 'g_u'), (g_x, (B, N + 1, 12), 'g_x')):
+            _check_tensor(t_, shp, nm, self.device, optional=True)
+        shapes = dict(x_in=(B, 12), x_ref=(B, N, 12), pf=(B, N, 3))
+        if out is None:
+            dev = x_in.device
+            out = {k: torch.empty(shapes[k], dtype=torch.float64, device=dev) if k in want else None for k in shapes}
+            out['flags'] = torch.empty(B, dtype=torch.int32, device=dev)
+        for k, shp in shapes.items():
+            _check_tensor(out.get(k), shp, f"out['{k}']", self.device, optional=True)
+        _check_tensor(out.get('flags'), (B,), "out['flags']", self.device, dtype='int32', optional=True)
+        s = stream if stream is not None else torch.cuda.current_stream(x_in.device).cuda_stream
+        rc = self._lib.hmpc_vjp_batch(self._h, B, _ptr(x_in), _ptr(x_lin), _ptr(x_ref), _ptr(pf), _ptr(C),
+                                      _ptr(mu), _ptr(u), _ptr(x), float(act_tol), _ptr(g_u), _ptr(g_x),
+                                      _ptr(out.get('x_in')), _ptr(out.get('x_ref')), _ptr(out.get('pf')),
+                                      _ptr(out.get('flags')), ctypes.c_void_p(s))
+        self._check(rc, 'hmpc_vjp_batch')
         return out
 
     def mpcontrol_device(self, init, x_in, x_ref, pf, C, x_prev, mu=None, out=None, stream=None):

@@ -33,6 +33,8 @@
  *                           for a given primal point, plus a KKT certificate
  *   hmpc_sens_batch      <- no reference analogue: the Jacobian d u* / d x_in of that
  *                           solve at its active set (feedback gain between solves)
+ *   hmpc_vjp_batch       <- no reference analogue: reverse-mode gradients of a loss on
+ *                           (u*, x*) with respect to x_in, x_ref and pf at that active set
  *   hmpc_destroy         <- object lifetime
  *
  * Conventions: every array is row-major, contiguous, float64, batch-major
@@ -109,8 +111,8 @@ typedef struct hmpc_ctx hmpc_ctx;
            kernel (capacity 64 at small batches);
    1.5.2 = the cross-stream completion event is recorded at a stream switch,
            not after every call (the last call's stream must stay valid);
-           + hmpc_kkt_batch, + hmpc_sens_batch (additions: the version number is
-           unchanged) */
+           + hmpc_kkt_batch, + hmpc_sens_batch, + hmpc_vjp_batch (additions: the
+           version number is unchanged) */
 int hmpc_version(void);
 
 /* Which horizons have a dedicated (one- or two-wavefront) kernel for
@@ -367,6 +369,33 @@ int hmpc_sens_batch(hmpc_ctx* ctx, int64_t B,
                     const double* pf, const double* C, const double* mu,
                     const double* u, const double* x, double act_tol,
                     int n_stages, double* S, int32_t* flags, void* stream);
+
+/* Reverse-mode gradients of the solve: for the cotangents g_u = dL/du* and
+   g_x = dL/dx* of a scalar loss,
+     grad_theta = (d u* / d theta)' g_u + (d x* / d theta)' g_x,   theta = x_in, x_ref, pf
+   at a primal point (x, u) of the QP hmpc_solve_batch solves, with x_lin, C and
+   mu held fixed.  The solution map is the one hmpc_sens_batch differentiates:
+   one QP with its active set held (slack <= act_tol (1 + |bound|), every active
+   row an equality, a stance stage with fz = 0 pins all three force components,
+   the z row of stage 0 is never held).  x*_0 = x_in, so g_x[:,0] reaches
+   grad_x_in directly.  Inputs as hmpc_sens_batch (device pointers), then
+     g_u        [B,N,6]     may be NULL (= 0)
+     g_x        [B,N+1,12]  may be NULL (= 0); not both NULL
+     grad_x_in  [B,12]      may be NULL (not computed)
+     grad_x_ref [B,N,12]    may be NULL
+     grad_pf    [B,N,3]     may be NULL; not all three NULL
+     flags      [B]         HMPC_VJP_SINGULAR as HMPC_SENS_SINGULAR; may be NULL
+   One adjoint solve per instance, whatever the number of parameters.  Serves
+   the 3f and 2f variants for 1 <= N <= 64 (else HMPC_ERR_UNSUPPORTED).
+   Asynchronous, allocates nothing (can be captured into a HIP graph). */
+#define HMPC_VJP_SINGULAR 1   /* a dependent active z row was dropped (as HMPC_SENS_SINGULAR) */
+int hmpc_vjp_batch(hmpc_ctx* ctx, int64_t B,
+                   const double* x_in, const double* x_lin, const double* x_ref,
+                   const double* pf, const double* C, const double* mu,
+                   const double* u, const double* x, double act_tol,
+                   const double* g_u, const double* g_x,
+                   double* grad_x_in, double* grad_x_ref, double* grad_pf,
+                   int32_t* flags, void* stream);
 
 /* Last HIP error string of this context ("" if none). */
 const char* hmpc_last_error(hmpc_ctx* ctx);
