@@ -1012,6 +1012,47 @@ int hmpc_vjp_batch(hmpc_ctx* c, int64_t B, const double* x_in, const double* x_l
   return mark_stream(c, (hipStream_t)stream);
 }
 
+int hmpc_vjp_lin_batch(hmpc_ctx* c, int64_t B, const double* x_in, const double* x_lin, const double* x_ref,
+                       const double* pf, const double* C, const double* mu, const double* u, const double* x,
+                       double act_tol, const double* nu, const double* lam, const double* g_u, const double* g_x,
+                       double* grad_x_in, double* grad_x_ref, double* grad_pf, double* grad_x_lin,
+                       double* grad_mu, int32_t* flags, void* stream) {
+  if (!c) return HMPC_ERR_ARG;
+  if (c->variant == HMPC_VARIANT_CAS || c->N > hmpc::kVjpNmax) {
+    c->err = "hmpc_vjp_lin_batch serves the 3f and 2f variants up to N = 64";
+    return HMPC_ERR_UNSUPPORTED;
+  }
+  if (B < 0 || !(act_tol >= 0.0)) { c->err = "B < 0 or act_tol < 0"; return HMPC_ERR_ARG; }
+  if (!g_u && !g_x) { c->err = "both cotangents are null"; return HMPC_ERR_ARG; }
+  if (!grad_x_in && !grad_x_ref && !grad_pf && !grad_x_lin && !grad_mu) {
+    c->err = "every gradient output is null";
+    return HMPC_ERR_ARG;
+  }
+  if (!nu || !lam) { c->err = "the multipliers nu and lam are required (hmpc_kkt_batch)"; return HMPC_ERR_ARG; }
+  if (B == 0) return HMPC_OK;
+  if (B > 0x7fffffffLL) { c->err = "B exceeds the grid limit"; return HMPC_ERR_ARG; }
+  if (!x_in || !x_lin || !x_ref || !pf || !C || !u || !x) { c->err = "null input pointer"; return HMPC_ERR_ARG; }
+  const void* ptrs[] = {x_in, x_lin, x_ref, pf, C, mu, u, x, nu, lam, g_u, g_x,
+                        grad_x_in, grad_x_ref, grad_pf, grad_x_lin, grad_mu};
+  for (const void* p : ptrs)
+    if ((uintptr_t)p % sizeof(double)) { c->err = "misaligned pointer"; return HMPC_ERR_ARG; }
+  HMPC_HIP(c, hipSetDevice(c->device));
+  hmpc::VjpLinArgs a;
+  a.x_lin = x_lin; a.x_ref = x_ref; a.pf = pf; a.C = C; a.mu = mu; a.u = u; a.x = x;
+  a.g_u = g_u; a.g_x = g_x;
+  a.grad_x_in = grad_x_in; a.grad_x_ref = grad_x_ref; a.grad_pf = grad_pf; a.flags = flags;
+  a.lam = lam; a.grad_x_lin = grad_x_lin; a.grad_mu = grad_mu;   // nu: see DESIGN.md 4.10 (no term reads it)
+  a.B = B; a.N = c->N;
+  a.dt = c->t; a.m = c->m; a.mu_default = c->mu; a.act_tol = act_tol;
+  memcpy(a.Jinv, c->Jinv, sizeof(a.Jinv));
+  memcpy(a.rh, c->rh, sizeof(a.rh));
+  int rc;
+  if ((rc = order_stream(c, (hipStream_t)stream)) != HMPC_OK) return rc;
+  hmpc::launch_vjp_lin(c->variant, a, (hipStream_t)stream);
+  HMPC_HIP(c, hipGetLastError());
+  return mark_stream(c, (hipStream_t)stream);
+}
+
 int hmpc_plan_batch(hmpc_ctx* c, int64_t B, int N_run, int N_k, double dt, int curve, double t_p,
                     double phi_switch, double t_start, int step_adjustment, const double* x_in,
                     const double* xf, double* x_ref, double* pf_ref, double* C_map, void* stream) {

@@ -251,7 +251,7 @@ struct SensArgs {
   double rh[3];
 };
 void launch_sens(int variant, const SensArgs& a, hipStream_t s);
-// Reverse-mode gradients of the solve at the same active set (hmpc_vjp.hip):
+// Reverse-mode gradients of the solve at the same active set (hmpc_vjp_kernel.h):
 // one wavefront per instance, 3f / 2f, 1 <= N <= kVjpNmax.
 constexpr int kVjpNmax = 64;
 struct VjpArgs {
@@ -275,6 +275,13 @@ struct VjpArgs {
   double rh[3];
 };
 void launch_vjp(int variant, const VjpArgs& a, hipStream_t s);
+// The same adjoint pass with the gradients in x_lin and mu (hmpc_vjp_lin.hip)
+struct VjpLinArgs : VjpArgs {
+  const double* lam;     // [B,N,11]  the primal point's multipliers (hmpc_kkt_batch)
+  double* grad_x_lin;    // [B,N+1,12] or nullptr
+  double* grad_mu;       // [B] or nullptr
+};
+void launch_vjp_lin(int variant, const VjpLinArgs& a, hipStream_t s);
 // the CasADi variant's kernel (hmpc_cas.hip): R slots of cas_ws_stride
 // doubles per resident workgroup in a.kws, instance counter a.work,
 // a.ric_groups workgroups

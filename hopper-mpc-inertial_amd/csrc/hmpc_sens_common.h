@@ -1,5 +1,5 @@
 // hmpc_sens_common.h -- device helpers the two kernels that differentiate the
-// solve share (hmpc_sens.hip: forward mode, hmpc_vjp.hip: reverse mode): the
+// solve share (hmpc_sens.hip: forward mode, hmpc_vjp_kernel.h: reverse mode): the
 // stage record, the projector Pi_k onto the free input directions, the 6 x 6
 // factor of G~_k on reciprocal pivots and Bd_k' times a costate
 // (DESIGN.md 4.8).  Device code only; internal linkage.

@@ -45,6 +45,7 @@ SIGNATURES = {
     'hmpc_sens_batch': (ctypes.c_int, [_VP, ctypes.c_int64] + [_VP] * 8 + [ctypes.c_double, ctypes.c_int]
                         + [_VP] * 2 + [_VP]),
     'hmpc_vjp_batch': (ctypes.c_int, [_VP, ctypes.c_int64] + [_VP] * 8 + [ctypes.c_double] + [_VP] * 6 + [_VP]),
+    'hmpc_vjp_lin_batch': (ctypes.c_int, [_VP, ctypes.c_int64] + [_VP] * 8 + [ctypes.c_double] + [_VP] * 10 + [_VP]),
     'hmpc_set_refinement': (ctypes.c_int, [_VP, ctypes.c_int]),
     'hmpc_set_order': (ctypes.c_int, [_VP, ctypes.c_int]),
     'hmpc_solve_batch_host': (ctypes.c_int, [_VP, ctypes.c_int64] + [_VP] * 11),
@@ -349,6 +350,42 @@ class Context:
                                       _ptr(out.get('x_in')), _ptr(out.get('x_ref')), _ptr(out.get('pf')),
                                       _ptr(out.get('flags')), ctypes.c_void_p(s))
         self._check(rc, 'hmpc_vjp_batch')
+        return out
+
+    def vjp_lin_device(self, x_in, x_lin, x_ref, pf, C, u, x, g_u=None, g_x=None, mu=None, act_tol=1e-8,
+                       nu=None, lam=None, want=('x_in', 'x_ref', 'pf', 'x_lin', 'mu'), out=None, stream=None):
+        """vjp_device with the gradients in x_lin (B,N+1,12; rows < N, columns 0:3
+        and 5 can be non-zero) and mu (B,) as well (hmpc_vjp_lin_batch).  nu (B,N)
+        and lam (B,N,11) are the primal point's multipliers as kkt_device returns
+        them; when either is None both are fetched by a kkt_device call on `stream`."""
+        import torch
+        N = self.N
+        B = x_in.shape[0]
+        for t_, shp, nm in ((x_in, (B, 12), 'x_in'), (x_lin, (B, N + 1, 12), 'x_lin'),
+                            (x_ref, (B, N, 12), 'x_ref'), (pf, (B, N, 3), 'pf'), (C, (B, N), 'C'),
+                            (u, (B, N, 6), 'u'), (x, (B, N + 1, 12), 'x')):
+            _check_tensor(t_, shp, nm, self.device)
+        for t_, shp, nm in ((mu, (B,), 'mu'), (g_u, (B, N, 6), 'g_u'), (g_x, (B, N + 1, 12), 'g_x'),
+                            (nu, (B, N), 'nu'), (lam, (B, N, 11), 'lam')):
+            _check_tensor(t_, shp, nm, self.device, optional=True)
+        shapes = dict(x_in=(B, 12), x_ref=(B, N, 12), pf=(B, N, 3), x_lin=(B, N + 1, 12), mu=(B,))
+        if out is None:
+            dev = x_in.device
+            out = {k: torch.empty(shapes[k], dtype=torch.float64, device=dev) if k in want else None for k in shapes}
+            out['flags'] = torch.empty(B, dtype=torch.int32, device=dev)
+        for k, shp in shapes.items():
+            _check_tensor(out.get(k), shp, f"out['{k}']", self.device, optional=True)
+        _check_tensor(out.get('flags'), (B,), "out['flags']", self.device, dtype='int32', optional=True)
+        if nu is None or lam is None:
+            kkt = self.kkt_device(x_in, x_lin, x_ref, pf, C, u, x, mu=mu, act_tol=act_tol, stream=stream)
+            nu, lam = kkt['nu'], kkt['lam']
+        s = stream if stream is not None else torch.cuda.current_stream(x_in.device).cuda_stream
+        rc = self._lib.hmpc_vjp_lin_batch(self._h, B, _ptr(x_in), _ptr(x_lin), _ptr(x_ref), _ptr(pf), _ptr(C),
+                                          _ptr(mu), _ptr(u), _ptr(x), float(act_tol), _ptr(nu), _ptr(lam),
+                                          _ptr(g_u), _ptr(g_x), _ptr(out.get('x_in')), _ptr(out.get('x_ref')),
+                                          _ptr(out.get('pf')), _ptr(out.get('x_lin')), _ptr(out.get('mu')),
+                                          _ptr(out.get('flags')), ctypes.c_void_p(s))
+        self._check(rc, 'hmpc_vjp_lin_batch')
         return out
 
     def mpcontrol_device(self, init, x_in, x_ref, pf, C, x_prev, mu=None, out=None, stream=None):

@@ -35,7 +35,11 @@
  *                           solve at its active set (feedback gain between solves)
  *   hmpc_vjp_batch       <- no reference analogue: reverse-mode gradients of a loss on
  *                           (u*, x*) with respect to x_in, x_ref and pf at that active set
- *   hmpc_destroy         <- object lifetime
+ *   hmpc_vjp_lin_batch   <- no reference analogue: the same pass with the gradients in
+ *                           x_lin and mu as well -- what backpropagation through
+ *                           Mpc.mpcontrol (src/mpc_cvx_euler_3f.py:41-69), whose x_guess
+ *                           depends on x_in and on the previous solve, needs
+ *   hmpc_destroy        <- object lifetime
  *
  * Conventions: every array is row-major, contiguous, float64, batch-major
  * (instance b's x_ref is x_ref[b*N*12 .. (b+1)*N*12)).  C holds the contact
@@ -111,8 +115,8 @@ typedef struct hmpc_ctx hmpc_ctx;
            kernel (capacity 64 at small batches);
    1.5.2 = the cross-stream completion event is recorded at a stream switch,
            not after every call (the last call's stream must stay valid);
-           + hmpc_kkt_batch, + hmpc_sens_batch, + hmpc_vjp_batch (additions: the
-           version number is unchanged) */
+           + hmpc_kkt_batch, + hmpc_sens_batch, + hmpc_vjp_batch,
+           + hmpc_vjp_lin_batch (additions: the version number is unchanged) */
 int hmpc_version(void);
 
 /* Which horizons have a dedicated (one- or two-wavefront) kernel for
@@ -396,6 +400,33 @@ int hmpc_vjp_batch(hmpc_ctx* ctx, int64_t B,
                    const double* g_u, const double* g_x,
                    double* grad_x_in, double* grad_x_ref, double* grad_pf,
                    int32_t* flags, void* stream);
+
+/* hmpc_vjp_batch with the gradients in the linearisation point and the friction
+   coefficient as well, from the same adjoint solve and the same solution map.
+   Inputs as hmpc_vjp_batch, and the multipliers of the primal point as
+   hmpc_kkt_batch writes them (device pointers, both required):
+     nu         [B,N]
+     lam        [B,N,11]
+   Outputs (each may be NULL, not all five):
+     grad_x_in, grad_x_ref, grad_pf   as hmpc_vjp_batch, bit for bit
+     grad_x_lin [B,N+1,12]  written in full: rows 0..N-1, columns 0:3 (position)
+                            and 5 (yaw) -- what gen_dt_dynamics reads -- carry the
+                            gradient, every other entry is 0.0
+     grad_mu    [B]         also written when mu is NULL (the context's default)
+     flags      [B]         HMPC_VJP_SINGULAR; may be NULL
+   With x_lin[:,0] = x_in and x_lin[:,1:] taken from an earlier solve these are the
+   terms a chain rule through Mpc.mpcontrol needs.  Serves the 3f and 2f variants
+   for 1 <= N <= 64 (else HMPC_ERR_UNSUPPORTED).  Asynchronous, allocates nothing
+   (can be captured into a HIP graph). */
+int hmpc_vjp_lin_batch(hmpc_ctx* ctx, int64_t B,
+                       const double* x_in, const double* x_lin, const double* x_ref,
+                       const double* pf, const double* C, const double* mu,
+                       const double* u, const double* x, double act_tol,
+                       const double* nu, const double* lam,
+                       const double* g_u, const double* g_x,
+                       double* grad_x_in, double* grad_x_ref, double* grad_pf,
+                       double* grad_x_lin, double* grad_mu,
+                       int32_t* flags, void* stream);
 
 /* Last HIP error string of this context ("" if none). */
 const char* hmpc_last_error(hmpc_ctx* ctx);
