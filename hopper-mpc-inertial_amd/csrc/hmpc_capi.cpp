@@ -902,6 +902,40 @@ int hmpc_plant_batch(hmpc_ctx* c, int64_t B, int n_steps, double dt, const doubl
   return HMPC_OK;
 }
 
+int hmpc_plant_vjp_batch(hmpc_ctx* c, int64_t B, int n_steps, double dt, const double* J, const double* X0,
+                         const double* X_hist, const double* U, int64_t U_bstride, const double* pf,
+                         int64_t pf_bstride, int64_t pf_sstride, const double* g_X, const double* g_x_out,
+                         const double* g_X_hist, double* grad_X0, double* grad_U, double* grad_pf,
+                         void* stream) {
+  if (!c) return HMPC_ERR_ARG;
+  if (B < 0 || n_steps < 0 || !(dt > 0.0)) { c->err = "B < 0, n_steps < 0 or dt <= 0"; return HMPC_ERR_ARG; }
+  if (U_bstride < 0 || pf_bstride < 0 || pf_sstride < 0) { c->err = "negative stride"; return HMPC_ERR_ARG; }
+  if (!g_X && !g_x_out && !g_X_hist) { c->err = "every cotangent is null"; return HMPC_ERR_ARG; }
+  if (!grad_X0 && !grad_U && !grad_pf) { c->err = "every gradient output is null"; return HMPC_ERR_ARG; }
+  if (n_steps == 0 && (g_X_hist || grad_pf)) {
+    c->err = "g_X_hist and grad_pf have no rows at n_steps = 0";
+    return HMPC_ERR_ARG;
+  }
+  if (B == 0) return HMPC_OK;
+  if (!J || !X0 || !U || !pf) { c->err = "null pointer"; return HMPC_ERR_ARG; }
+  if (n_steps >= 2 && !X_hist) { c->err = "X_hist is required for n_steps >= 2"; return HMPC_ERR_ARG; }
+  HMPC_HIP(c, hipSetDevice(c->device));
+  hmpc::PlantVjpArgs a;
+  a.B = B; a.n_steps = n_steps; a.dt = dt; a.m = c->m; a.g = c->g;
+  memcpy(a.J, J, sizeof(a.J));
+  memcpy(a.Jinv, c->Jinv, sizeof(a.Jinv));
+  memcpy(a.rh, c->rh, sizeof(a.rh));
+  a.X = nullptr; a.X_hist = nullptr; a.x_out = nullptr;
+  a.U = U; a.U_bs = U_bstride;
+  a.pf = pf; a.pf_bs = pf_bstride; a.pf_ss = pf_sstride;
+  a.X0 = X0; a.Xh = X_hist;
+  a.g_X = g_X; a.g_x_out = g_x_out; a.g_X_hist = g_X_hist;
+  a.grad_X0 = grad_X0; a.grad_U = grad_U; a.grad_pf = grad_pf;
+  hmpc::launch_plant_vjp(a, (hipStream_t)stream);
+  HMPC_HIP(c, hipGetLastError());
+  return HMPC_OK;
+}
+
 int hmpc_convert_batch(hmpc_ctx* c, int64_t B, const double* X, double* x, void* stream) {
   if (!c) return HMPC_ERR_ARG;
   if (B < 0) { c->err = "B < 0"; return HMPC_ERR_ARG; }

@@ -208,6 +208,20 @@ struct PlantArgs {
 };
 void launch_plant(const PlantArgs& a, hipStream_t s);
 void launch_convert(int64_t B, const double* X, double* x, hipStream_t s);
+// The adjoint of one launch_plant call, and of convert (hmpc_plant_vjp.hip):
+// one lane per robot.  The PlantArgs part carries the constants and the U / pf
+// views of the forward call; its X, X_hist and x_out are not used.
+struct PlantVjpArgs : PlantArgs {
+  const double* X0;        // [B,13] the state before the forward call
+  const double* Xh;        // [B,n_steps,13] the forward's X_hist (rows 0..n_steps-2 are read), or nullptr
+  const double* g_X;       // [B,13] or nullptr (= 0)
+  const double* g_x_out;   // [B,12] or nullptr (= 0)
+  const double* g_X_hist;  // [B,n_steps,13] or nullptr (= 0)
+  double* grad_X0;         // [B,13] or nullptr
+  double* grad_U;          // [B,6] or nullptr
+  double* grad_pf;         // [B,n_steps,3] or nullptr
+};
+void launch_plant_vjp(const PlantVjpArgs& a, hipStream_t s);
 // Multipliers and KKT certificate of a given primal point (hmpc_kkt.hip): one
 // wavefront per instance, 3f / 2f, 1 <= N <= kKktNmax.
 constexpr int kKktNmax = 64;

@@ -57,6 +57,9 @@ SIGNATURES = {
     'hmpc_plant_batch': (ctypes.c_int, [_VP, ctypes.c_int64, ctypes.c_int, ctypes.c_double, _D, _VP,
                                         _VP, ctypes.c_int64, _VP, ctypes.c_int64, ctypes.c_int64,
                                         _VP, _VP, _VP]),
+    'hmpc_plant_vjp_batch': (ctypes.c_int, [_VP, ctypes.c_int64, ctypes.c_int, ctypes.c_double, _D, _VP, _VP,
+                                            _VP, ctypes.c_int64, _VP, ctypes.c_int64, ctypes.c_int64]
+                             + [_VP] * 6 + [_VP]),
     'hmpc_convert_batch': (ctypes.c_int, [_VP, ctypes.c_int64, _VP, _VP, _VP]),
     'hmpc_plan_batch': (ctypes.c_int, [_VP, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                        ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
@@ -477,6 +480,39 @@ class Context:
                                         int(pf_sstride), _ptr(X_hist), _ptr(x_out),
                                         ctypes.c_void_p(s))
         self._check(rc, 'hmpc_plant_batch')
+
+    def plant_vjp_device(self, X0, X_hist, U, U_bstride, pf, pf_bstride, pf_sstride, n_steps, dt, J,
+                         g_X=None, g_x_out=None, g_X_hist=None, want=('X0', 'U', 'pf'), stream=None):
+        """Reverse-mode gradients of one plant_device call (hmpc_plant_vjp_batch): X0 (B,13) is
+        the state before that call, X_hist (B,n_steps,13) what it recorded (None for
+        n_steps <= 1), U / pf and their strides as passed to it.  g_X (B,13), g_x_out (B,12)
+        and g_X_hist (B,n_steps,13) are the cotangents (None = 0).  Returns the gradients
+        named in `want`: X0 (B,13), U (B,6), pf (B,n_steps,3); n_steps = 0 is convert's."""
+        import torch
+        B, n = X0.shape[0], int(n_steps)
+        _check_tensor(X0, (B, 13), 'X0', self.device)
+        for t_, nm in ((U, 'U'), (pf, 'pf')):
+            _check_tensor(t_, tuple(t_.shape), nm, self.device)
+        if U.numel() < (B - 1) * int(U_bstride) + 6:
+            raise ValueError('U is too small for B rows at U_bstride')
+        if pf.numel() < (B - 1) * int(pf_bstride) + (n - 1) * int(pf_sstride) + 3:
+            raise ValueError('pf is too small for B robots x n_steps at the given strides')
+        _check_tensor(X_hist, (B, n, 13), 'X_hist', self.device, optional=n < 2)
+        for t_, shp, nm in ((g_X, (B, 13), 'g_X'), (g_x_out, (B, 12), 'g_x_out'),
+                            (g_X_hist, (B, n, 13), 'g_X_hist')):
+            _check_tensor(t_, shp, nm, self.device, optional=True)
+        shapes = dict(X0=(B, 13), U=(B, 6), pf=(B, n, 3))
+        out = {k: torch.empty(shapes[k], dtype=torch.float64, device=X0.device) if k in want else None
+               for k in shapes}
+        Jh = np.ascontiguousarray(np.asarray(J, dtype=np.float64).reshape(9))
+        s = stream if stream is not None else torch.cuda.current_stream(X0.device).cuda_stream
+        rc = self._lib.hmpc_plant_vjp_batch(self._h, B, n, float(dt), Jh.ctypes.data_as(_D), _ptr(X0),
+                                            _ptr(X_hist), _ptr(U), int(U_bstride), _ptr(pf), int(pf_bstride),
+                                            int(pf_sstride), _ptr(g_X), _ptr(g_x_out), _ptr(g_X_hist),
+                                            _ptr(out['X0']), _ptr(out['U']), _ptr(out['pf']),
+                                            ctypes.c_void_p(s))
+        self._check(rc, 'hmpc_plant_vjp_batch')
+        return out
 
     def plan_device(self, x_in, xf, N_run, N_k, dt, curve, t_p, phi_switch, t_start, step_adjustment,
                     stream=None):

@@ -39,6 +39,9 @@
  *                           x_lin and mu as well -- what backpropagation through
  *                           Mpc.mpcontrol (src/mpc_cvx_euler_3f.py:41-69), whose x_guess
  *                           depends on x_in and on the previous solve, needs
+ *   hmpc_plant_vjp_batch <- no reference analogue: the adjoint of rk4_normalized / convert
+ *                           (src/robotrunner.py:154-164, :19-28), so that a loss on the
+ *                           closed-loop trajectory reaches the plan and the start state
  *   hmpc_destroy        <- object lifetime
  *
  * Conventions: every array is row-major, contiguous, float64, batch-major
@@ -116,7 +119,8 @@ typedef struct hmpc_ctx hmpc_ctx;
    1.5.2 = the cross-stream completion event is recorded at a stream switch,
            not after every call (the last call's stream must stay valid);
            + hmpc_kkt_batch, + hmpc_sens_batch, + hmpc_vjp_batch,
-           + hmpc_vjp_lin_batch (additions: the version number is unchanged) */
+           + hmpc_vjp_lin_batch, + hmpc_plant_vjp_batch (additions: the version number
+           is unchanged) */
 int hmpc_version(void);
 
 /* Which horizons have a dedicated (one- or two-wavefront) kernel for
@@ -227,6 +231,34 @@ int hmpc_plant_batch(hmpc_ctx* ctx, int64_t B, int n_steps, double dt, const dou
 
 /* x [B,12] = convert(X [B,13]) (src/robotrunner.py:19-28).  Asynchronous. */
 int hmpc_convert_batch(hmpc_ctx* ctx, int64_t B, const double* X, double* x, void* stream);
+
+/* Reverse-mode gradients of one hmpc_plant_batch call: the adjoint of n_steps of
+   rk4_normalized (src/robotrunner.py:154-164) and of the convert (:19-28) that
+   follows them.  Inputs are that call's (device pointers; J host):
+     X0         [B,13]          the state before the call
+     X_hist     [B,n_steps,13]  the call's X_hist (required when n_steps >= 2: the
+                                checkpoints; its last row is not read)
+     U, pf      addressed exactly as in hmpc_plant_batch
+   Cotangents (each may be NULL = 0, not all three):
+     g_X        [B,13]          on the final state
+     g_x_out    [B,12]          on convert(final state)
+     g_X_hist   [B,n_steps,13]  on every step's state (its last row adds to g_X)
+   Outputs (each may be NULL, not all three):
+     grad_X0    [B,13]          all four quaternion components are independent
+     grad_U     [B,6]           the held input
+     grad_pf    [B,n_steps,3]   per robot and step, whatever strides pf was read with
+   dt, J, m, g and rh are constants.  n_steps = 0 is the adjoint of hmpc_convert_batch
+   (g_x_out) with g_X added to grad_X0; g_X_hist and grad_pf must then be NULL.  convert
+   is differentiated along the branch it took; at its gimbal branch (cos(pitch) <= 4 eps)
+   it is not differentiable: the yaw contributes 0 and the result is otherwise undefined.
+   Serves every context (CAS included), like hmpc_plant_batch.  Asynchronous, allocates
+   nothing (can be captured into a HIP graph). */
+int hmpc_plant_vjp_batch(hmpc_ctx* ctx, int64_t B, int n_steps, double dt, const double* J,
+                         const double* X0, const double* X_hist,
+                         const double* U, int64_t U_bstride,
+                         const double* pf, int64_t pf_bstride, int64_t pf_sstride,
+                         const double* g_X, const double* g_x_out, const double* g_X_hist,
+                         double* grad_X0, double* grad_U, double* grad_pf, void* stream);
 
 /* Runner.path_plan_init (src/robotrunner.py:182-226) for B robots on the
    device: robot b's plan from its own start x_in[b] and goal xf[b] (convert()ed
