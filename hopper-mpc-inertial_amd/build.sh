@@ -113,6 +113,9 @@ pids+=($!)
 # the adjoint of the plant and of convert (hmpc_plant_vjp_batch): a new object, same rule
 $HIPCC $FLAGS -Xclang -target-feature -Xclang -packed-fp32-ops -c csrc/hmpc_plant_vjp.hip -o $BDIR/hmpc_plant_vjp.o &
 pids+=($!)
+# the plant under the K_0 feedback law (hmpc_plant_fb_batch): a new object, same rule
+$HIPCC $FLAGS -Xclang -target-feature -Xclang -packed-fp32-ops -c csrc/hmpc_plant_fb.hip -o $BDIR/hmpc_plant_fb.o &
+pids+=($!)
 $HIPCC $FLAGS -c csrc/hmpc_cas.hip -o $BDIR/hmpc_cas.o "$@" &
 pids+=($!)
 $HIPCC $FLAGS -c csrc/hmpc_wide.hip -o $BDIR/hmpc_wide.o "$@" &
@@ -126,7 +129,7 @@ objs="$objs $CMPOBJS"
 for n in $F32_HORIZONS; do objs="$objs $BDIR/hmpc_kernels_n${n}_f32.o $BDIR/hmpc_kernels_n${n}_f32r.o"; done
 # every object but the ABI/dispatch host code, for tests/test_sanitizers.py (which
 # rebuilds those two under ASan/UBSan and links the kernels as built)
-echo $objs $BDIR/hmpc_plant.o $BDIR/hmpc_kkt.o $BDIR/hmpc_sens.o $BDIR/hmpc_vjp.o $BDIR/hmpc_vjp_lin.o $BDIR/hmpc_plant_vjp.o $BDIR/hmpc_planner.o $BDIR/hmpc_cas.o $BDIR/hmpc_wide.o $BDIR/hmpc_ric.o | tr ' ' '\n' > $BDIR/objs.txt
-$HIPCC --offload-arch=gfx950 -shared -fPIC $objs $BDIR/hmpc_dispatch.o $BDIR/hmpc_capi.o $BDIR/hmpc_plant.o $BDIR/hmpc_kkt.o $BDIR/hmpc_sens.o $BDIR/hmpc_vjp.o $BDIR/hmpc_vjp_lin.o $BDIR/hmpc_plant_vjp.o $BDIR/hmpc_planner.o $BDIR/hmpc_cas.o $BDIR/hmpc_wide.o $BDIR/hmpc_ric.o -o $OUT.tmp
+echo $objs $BDIR/hmpc_plant.o $BDIR/hmpc_kkt.o $BDIR/hmpc_sens.o $BDIR/hmpc_vjp.o $BDIR/hmpc_vjp_lin.o $BDIR/hmpc_plant_vjp.o $BDIR/hmpc_plant_fb.o $BDIR/hmpc_planner.o $BDIR/hmpc_cas.o $BDIR/hmpc_wide.o $BDIR/hmpc_ric.o | tr ' ' '\n' > $BDIR/objs.txt
+$HIPCC --offload-arch=gfx950 -shared -fPIC $objs $BDIR/hmpc_dispatch.o $BDIR/hmpc_capi.o $BDIR/hmpc_plant.o $BDIR/hmpc_kkt.o $BDIR/hmpc_sens.o $BDIR/hmpc_vjp.o $BDIR/hmpc_vjp_lin.o $BDIR/hmpc_plant_vjp.o $BDIR/hmpc_plant_fb.o $BDIR/hmpc_planner.o $BDIR/hmpc_cas.o $BDIR/hmpc_wide.o $BDIR/hmpc_ric.o -o $OUT.tmp
 mv $OUT.tmp $OUT
 echo "built $(pwd)/$OUT (horizons: $HORIZONS)"

@@ -936,6 +936,44 @@ int hmpc_plant_vjp_batch(hmpc_ctx* c, int64_t B, int n_steps, double dt, const d
   return HMPC_OK;
 }
 
+int hmpc_plant_fb_batch(hmpc_ctx* c, int64_t B, int n_steps, int stage_steps, double dt, const double* J,
+                        double* X, const double* U, int64_t U_bstride, const double* K, int64_t K_bstride,
+                        const double* x_nom, int64_t xnom_bstride, const double* pf, int64_t pf_bstride,
+                        int64_t pf_sstride, const double* C0, int64_t C0_bstride, const double* mu, int flags,
+                        double* X_hist, double* U_hist, double* x_out, int32_t* sat, void* stream) {
+  if (!c) return HMPC_ERR_ARG;
+  if (B < 0 || n_steps < 1 || stage_steps < 1 || !(dt > 0.0)) {
+    c->err = "B < 0, n_steps < 1, stage_steps < 1 or dt <= 0";
+    return HMPC_ERR_ARG;
+  }
+  if (flags & ~(HMPC_FB_CLIP | HMPC_FB_INTERP)) { c->err = "unknown flag bits"; return HMPC_ERR_ARG; }
+  if (U_bstride < 0 || K_bstride < 0 || xnom_bstride < 0 || pf_bstride < 0 || pf_sstride < 0 || C0_bstride < 0) {
+    c->err = "negative stride";
+    return HMPC_ERR_ARG;
+  }
+  if (B == 0) return HMPC_OK;
+  if (!J || !X || !U || !K || !x_nom || !pf) { c->err = "null pointer"; return HMPC_ERR_ARG; }
+  HMPC_HIP(c, hipSetDevice(c->device));
+  hmpc::PlantFbArgs a;
+  a.B = B; a.n_steps = n_steps; a.dt = dt; a.m = c->m; a.g = c->g;
+  memcpy(a.J, J, sizeof(a.J));
+  memcpy(a.Jinv, c->Jinv, sizeof(a.Jinv));
+  memcpy(a.rh, c->rh, sizeof(a.rh));
+  a.X = X; a.U = U; a.U_bs = U_bstride;
+  a.pf = pf; a.pf_bs = pf_bstride; a.pf_ss = pf_sstride;
+  a.X_hist = X_hist; a.x_out = x_out;
+  a.stage_steps = stage_steps; a.flags = flags;
+  a.fy_zero = c->variant == HMPC_VARIANT_2F ? 1 : 0;
+  a.K = K; a.K_bs = K_bstride;
+  a.x_nom = x_nom; a.xnom_bs = xnom_bstride;
+  a.C0 = C0; a.C0_bs = C0_bstride;
+  a.mu = mu; a.mu_default = c->mu;
+  a.U_hist = U_hist; a.sat = sat;
+  hmpc::launch_plant_fb(a, (hipStream_t)stream);
+  HMPC_HIP(c, hipGetLastError());
+  return HMPC_OK;
+}
+
 int hmpc_convert_batch(hmpc_ctx* c, int64_t B, const double* X, double* x, void* stream) {
   if (!c) return HMPC_ERR_ARG;
   if (B < 0) { c->err = "B < 0"; return HMPC_ERR_ARG; }

@@ -222,6 +222,25 @@ struct PlantVjpArgs : PlantArgs {
   double* grad_pf;         // [B,n_steps,3] or nullptr
 };
 void launch_plant_vjp(const PlantVjpArgs& a, hipStream_t s);
+// The plant under the feedback law u_s = clip(U + K (convert(X_s) - xbar_s))
+// (hmpc_plant_fb.hip): one lane per robot, the gains through LDS.  The
+// PlantArgs part is the forward call's (U: the nominal input u*_0).
+struct PlantFbArgs : PlantArgs {
+  int stage_steps;         // low-level steps per MPC stage (the interpolation's denominator)
+  int flags;               // HMPC_FB_CLIP | HMPC_FB_INTERP
+  int fy_zero;             // the 2f input set: fy = 0
+  const double* K;         // robot b's [6][12] gain at K + b*K_bs
+  int64_t K_bs;
+  const double* x_nom;     // rows 0, 1 ([2][12]) at x_nom + b*xnom_bs
+  int64_t xnom_bs;
+  const double* C0;        // contact flag of the period at C0 + b*C0_bs, or nullptr (stance)
+  int64_t C0_bs;
+  const double* mu;        // [B] or nullptr
+  double mu_default;
+  double* U_hist;          // [B,n_steps,6] the applied inputs, or nullptr
+  int32_t* sat;            // [B] steps in which the clip moved a component, or nullptr
+};
+void launch_plant_fb(const PlantFbArgs& a, hipStream_t s);
 // Multipliers and KKT certificate of a given primal point (hmpc_kkt.hip): one
 // wavefront per instance, 3f / 2f, 1 <= N <= kKktNmax.
 constexpr int kKktNmax = 64;

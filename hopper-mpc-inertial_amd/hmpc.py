@@ -21,6 +21,7 @@ ERRORS = {-1: 'HMPC_ERR_ARG', -2: 'HMPC_ERR_UNSUPPORTED', -3: 'HMPC_ERR_HIP', -4
 KKT_SINGULAR = 1   # kkt_device flags: dependent active z rows (HMPC_KKT_SINGULAR)
 SENS_SINGULAR, SENS_ZROWS = 1, 2   # sens_device flags (HMPC_SENS_SINGULAR, HMPC_SENS_ZROWS)
 VJP_SINGULAR = 1   # vjp_device flags (HMPC_VJP_SINGULAR)
+FB_CLIP, FB_INTERP = 1, 2   # plant_fb_device flags (HMPC_FB_CLIP, HMPC_FB_INTERP)
 STATUS = {0: 'solved', 1: 'max_iter', 2: 'primal_infeasible', 3: 'numerical'}
 VARIANTS = {'3f': 3, '2f': 2, 'cas': 4, 3: 3, 2: 2, 4: 4}
 UREF = {'aliased': 0, 'per_stage': 1}
@@ -60,6 +61,9 @@ SIGNATURES = {
     'hmpc_plant_vjp_batch': (ctypes.c_int, [_VP, ctypes.c_int64, ctypes.c_int, ctypes.c_double, _D, _VP, _VP,
                                             _VP, ctypes.c_int64, _VP, ctypes.c_int64, ctypes.c_int64]
                              + [_VP] * 6 + [_VP]),
+    'hmpc_plant_fb_batch': (ctypes.c_int, [_VP, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double, _D, _VP]
+                            + [_VP, ctypes.c_int64] * 3 + [_VP, ctypes.c_int64, ctypes.c_int64, _VP, ctypes.c_int64,
+                                                           _VP, ctypes.c_int] + [_VP] * 4 + [_VP]),
     'hmpc_convert_batch': (ctypes.c_int, [_VP, ctypes.c_int64, _VP, _VP, _VP]),
     'hmpc_plan_batch': (ctypes.c_int, [_VP, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                        ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
@@ -480,6 +484,48 @@ class Context:
                                         int(pf_sstride), _ptr(X_hist), _ptr(x_out),
                                         ctypes.c_void_p(s))
         self._check(rc, 'hmpc_plant_batch')
+
+    def plant_fb_device(self, X, U, U_bstride, K, K_bstride, x_nom, xnom_bstride, pf, pf_bstride, pf_sstride,
+                        n_steps, stage_steps, dt, J, C0=None, C0_bstride=0, mu=None, flags=0, X_hist=None,
+                        U_hist=None, x_out=None, sat=None, stream=None):
+        """plant_device under the feedback law u_s = clip(U + K (convert(X_s) - xbar_s))
+        (hmpc_plant_fb_batch): K holds a (6,12) gain per robot (sens_device's S with
+        n_stages = 1 and K_bstride = 72), x_nom rows 0 and 1 of the nominal trajectory (x*
+        with xnom_bstride = 12 (N+1)), C0 the period's contact flag per robot (None = stance);
+        flags is FB_CLIP | FB_INTERP.  U_hist (B,n_steps,6) receives the applied inputs, sat
+        (B,) int32 the number of steps the clip was active in; see the header for the strides."""
+        import torch
+        B, n, flags = X.shape[0], int(n_steps), int(flags)
+        _check_tensor(X, (B, 13), 'X', self.device)
+        for t_, nm in ((U, 'U'), (K, 'K'), (x_nom, 'x_nom'), (pf, 'pf')):
+            _check_tensor(t_, None if t_ is None else tuple(t_.shape), nm, self.device)
+        _check_tensor(C0, None if C0 is None else tuple(C0.shape), 'C0', self.device, optional=True)
+        if min(int(U_bstride), int(K_bstride), int(xnom_bstride), int(pf_bstride), int(pf_sstride),
+               int(C0_bstride)) < 0:
+            raise ValueError('strides must be >= 0')
+        if U.numel() < (B - 1) * int(U_bstride) + 6:
+            raise ValueError('U is too small for B rows at U_bstride')
+        if K.numel() < (B - 1) * int(K_bstride) + 72:
+            raise ValueError('K is too small for B gains at K_bstride')
+        if x_nom.numel() < (B - 1) * int(xnom_bstride) + (24 if flags & FB_INTERP else 12):
+            raise ValueError('x_nom is too small for B robots at xnom_bstride')
+        if pf.numel() < (B - 1) * int(pf_bstride) + (n - 1) * int(pf_sstride) + 3:
+            raise ValueError('pf is too small for B robots x n_steps at the given strides')
+        if C0 is not None and C0.numel() < (B - 1) * int(C0_bstride) + 1:
+            raise ValueError('C0 is too small for B robots at C0_bstride')
+        _check_tensor(mu, (B,), 'mu', self.device, optional=True)
+        _check_tensor(X_hist, (B, n, 13), 'X_hist', self.device, optional=True)
+        _check_tensor(U_hist, (B, n, 6), 'U_hist', self.device, optional=True)
+        _check_tensor(x_out, (B, 12), 'x_out', self.device, optional=True)
+        _check_tensor(sat, (B,), 'sat', self.device, dtype='int32', optional=True)
+        Jh = np.ascontiguousarray(np.asarray(J, dtype=np.float64).reshape(9))
+        s = stream if stream is not None else torch.cuda.current_stream(X.device).cuda_stream
+        rc = self._lib.hmpc_plant_fb_batch(self._h, B, n, int(stage_steps), float(dt), Jh.ctypes.data_as(_D),
+                                           _ptr(X), _ptr(U), int(U_bstride), _ptr(K), int(K_bstride),
+                                           _ptr(x_nom), int(xnom_bstride), _ptr(pf), int(pf_bstride),
+                                           int(pf_sstride), _ptr(C0), int(C0_bstride), _ptr(mu), flags,
+                                           _ptr(X_hist), _ptr(U_hist), _ptr(x_out), _ptr(sat), ctypes.c_void_p(s))
+        self._check(rc, 'hmpc_plant_fb_batch')
 
     def plant_vjp_device(self, X0, X_hist, U, U_bstride, pf, pf_bstride, pf_sstride, n_steps, dt, J,
                          g_X=None, g_x_out=None, g_X_hist=None, want=('X0', 'U', 'pf'), stream=None):

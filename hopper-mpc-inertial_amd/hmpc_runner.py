@@ -18,6 +18,12 @@ launches and no host work; ``run(graph=True)`` replays the whole run as
 one captured HIP graph.
 Plots are out of scope.
 
+``Runner(..., feedback=True)`` (no reference analogue) applies the
+feedback law of the solve's own gain between solves instead of holding u*_0: a
+period is then ``hmpc_solve_batch`` on the time-shifted linearisation,
+``hmpc_sens_batch`` for K_0 = d u*_0 / d x_in and ``hmpc_plant_fb_batch``, whose
+every low-level step applies u = clip(u*_0 + K_0 (x - x_nom)).
+
 There is no CPU fallback: without libhmpc.so or a GPU this raises.
 """
 from __future__ import annotations
@@ -36,10 +42,11 @@ class Runner:
     :46); ``X0`` (13,) or (batch, 13) overrides the start state X_0 (:57)."""
 
     def __init__(self, dt=1e-3, dyn='2f', curve=False, N_run=5000, N=60, batch=1, X0=None, mu=1.0,
-                 uref_mode='aliased', device=0):
+                 uref_mode='aliased', device=0, feedback=False):
         import torch
         self.cfg = hp.RunnerConfig(dt=dt, N_run=N_run, curve=curve, N=N)
         self.dyn = dyn
+        self.feedback = bool(feedback)
         self.B = int(batch)
         self.device = torch.device('cuda', device)
         c = hp.runner_constants()                                              # :37-48
@@ -160,6 +167,19 @@ class Runner:
                  f_hist=torch.empty((B, steps, 6), **f64) if record else None,
                  hist=torch.empty((B, mf, 13), **f64) if record else None,
                  status=torch.empty((len(call_k), B), dtype=torch.int32, device=dev))
+        if self.feedback:
+            P = len(call_k)
+            S['out']['x'] = torch.empty((B, N + 1, 12), **f64)
+            S.update(x_ref_w=torch.empty((B, N, 12), **f64), pf_w=torch.empty((B, N, 3), **f64),
+                     C_w=torch.empty((B, N), **f64), x_lin=torch.empty((B, N + 1, 12), **f64),
+                     st0=torch.empty(B, dtype=torch.int32, device=dev),
+                     sens=dict(S=torch.empty((B, 1, 6, 12), **f64),
+                               flags=torch.empty(B, dtype=torch.int32, device=dev)),
+                     u_hist=torch.empty((B, mf, 6), **f64) if record else None,
+                     sat=torch.empty((P, B), dtype=torch.int32, device=dev))
+            if record:   # what each period's plant call read
+                S['fb'] = dict(U0=torch.empty((P, B, 6), **f64), K=torch.empty((P, B, 6, 12), **f64),
+                               x_nom=torch.empty((P, B, 2, 12), **f64), C0=torch.empty((P, B), **f64))
         return S
 
     def _replan(self, S):
@@ -191,6 +211,8 @@ class Runner:
         X_traj, f_hist, hist = S['X_traj'], S['f_hist'], S['hist']
         if record:
             X_traj[:, 0] = X
+        if self.feedback:
+            return self._enqueue_feedback(S)
         for p, k in enumerate(S['call_k']):
             self.ctx.mpcontrol_plan_device(p == 0, x_in, plan_x, plan_pf, k, mf, S['C_all'][p], x_prev,
                                            out=out)                             # :98-103
@@ -201,6 +223,48 @@ class Runner:
             if record:
                 X_traj[:, k + 1:k + 1 + n] = hist[:, :n]
                 f_hist[:, k:k + n] = out['u'][:, 0:1, :]
+
+    def _enqueue_feedback(self, S):
+        """The periods of ``feedback=True``: Mpc.mpcontrol (src/mpc_cvx_euler_3f.py:41-69) spelled
+        out as solves on contiguous windows of the plan, so that x* and the gain K_0 at it are at
+        hand, then the plant under u = clip(u*_0 + K_0 (x - x_nom))."""
+        import torch
+        cfg, ctx = self.cfg, self.ctx
+        N, mf, dt = cfg.N, cfg.mpc_factor, cfg.dt
+        steps, record = S['steps'], S['record']
+        X, x_in, out, x_lin = S['X'], S['x_in'], S['out'], S['x_lin']
+        x_ref, pf, C = S['x_ref_w'], S['pf_w'], S['C_w']
+        plan_x, plan_pf = S['plan_x'], S['plan_pf']
+        pf_flat = plan_pf.reshape(-1)
+        pf_bs = 0 if S['shared'] else 3 * plan_x.shape[-2]
+        K = S['sens']['S']
+        for p, k in enumerate(S['call_k']):
+            x_ref.copy_(plan_x[..., k:k + N * mf:mf, :])                          # path_plan_grab (:98-101)
+            pf.copy_(plan_pf[..., k:k + N * mf:mf, :])
+            C.copy_(S['C_all'][p])
+            x_lin[:, 0] = x_in
+            if p == 0:   # init: the first solve's x* is the second's linearisation
+                x_lin[:, 1:] = x_ref
+                ctx.solve_device(x_in, x_lin, x_ref, pf, C, out=out)
+                S['st0'].copy_(out['status'])
+                x_lin.copy_(out['x'])
+            else:        # the time shift of the previous x*
+                x_lin[:, 1:N] = out['x'][:, 2:]
+                x_lin[:, N] = out['x'][:, N]
+            ctx.solve_device(x_in, x_lin, x_ref, pf, C, out=out)
+            S['status'][p] = out['status'] if p else torch.maximum(S['st0'], out['status'])
+            ctx.sens_device(x_in, x_lin, x_ref, pf, C, out['u'], out['x'], n_stages=1, out=S['sens'])
+            n = min(mf, steps - k)
+            if record:
+                fb = S['fb']
+                fb['U0'][p], fb['K'][p], fb['x_nom'][p], fb['C0'][p] = out['u'][:, 0], K[:, 0], out['x'][:, :2], C[:, 0]
+            ctx.plant_fb_device(X, out['u'], 6 * N, K, 72, out['x'], 12 * (N + 1), pf_flat[3 * k:], pf_bs, 3, n,
+                                mf, dt, self.J, C0=C, C0_bstride=N, flags=hmpc.FB_CLIP | hmpc.FB_INTERP,
+                                X_hist=S['hist'] if record else None, U_hist=S['u_hist'], x_out=x_in,
+                                sat=S['sat'][p])
+            if record:
+                S['X_traj'][:, k + 1:k + 1 + n] = S['hist'][:, :n]
+                S['f_hist'][:, k:k + n] = S['u_hist'][:, :n]
 
     def _finish(self, S):
         import torch
@@ -216,6 +280,10 @@ class Runner:
         if S['record']:
             res['X_traj'] = S['X_traj'].cpu().numpy()
             res['f_hist'] = S['f_hist'].cpu().numpy()
+        if self.feedback:
+            res['sat'] = S['sat'].cpu().numpy()
+            if S['record']:
+                res.update({k: v.cpu().numpy() for k, v in S['fb'].items()})
         return res
 
 

@@ -42,6 +42,9 @@
  *   hmpc_plant_vjp_batch <- no reference analogue: the adjoint of rk4_normalized / convert
  *                           (src/robotrunner.py:154-164, :19-28), so that a loss on the
  *                           closed-loop trajectory reaches the plan and the start state
+ *   hmpc_plant_fb_batch  <- no reference analogue: hmpc_plant_batch with the input of every
+ *                           low-level step corrected by hmpc_sens_batch's K_0 (the reference
+ *                           holds u*_0 over the period, src/robotrunner.py:104-113)
  *   hmpc_destroy        <- object lifetime
  *
  * Conventions: every array is row-major, contiguous, float64, batch-major
@@ -119,8 +122,8 @@ typedef struct hmpc_ctx hmpc_ctx;
    1.5.2 = the cross-stream completion event is recorded at a stream switch,
            not after every call (the last call's stream must stay valid);
            + hmpc_kkt_batch, + hmpc_sens_batch, + hmpc_vjp_batch,
-           + hmpc_vjp_lin_batch, + hmpc_plant_vjp_batch (additions: the version number
-           is unchanged) */
+           + hmpc_vjp_lin_batch, + hmpc_plant_vjp_batch, + hmpc_plant_fb_batch (additions:
+           the version number is unchanged) */
 int hmpc_version(void);
 
 /* Which horizons have a dedicated (one- or two-wavefront) kernel for
@@ -259,6 +262,47 @@ int hmpc_plant_vjp_batch(hmpc_ctx* ctx, int64_t B, int n_steps, double dt, const
                          const double* pf, int64_t pf_bstride, int64_t pf_sstride,
                          const double* g_X, const double* g_x_out, const double* g_X_hist,
                          double* grad_X0, double* grad_U, double* grad_pf, void* stream);
+
+/* hmpc_plant_batch under the feedback law of hmpc_sens_batch's gain (no reference analogue:
+   the reference holds u*_0 for the whole MPC period).  Low-level step s = 0 .. n_steps-1 of
+   robot b applies
+     x_s  = convert(X_s)
+     xbar = x_nom[b,0] + (s / stage_steps) (x_nom[b,1] - x_nom[b,0])   with HMPC_FB_INTERP,
+            else x_nom[b,0]
+     d    = x_s - xbar,  d[5] -= 2 pi rint(d[5] / 2 pi)                (the yaw only)
+     u_s  = U[b] + K[b] d,  clipped with HMPC_FB_CLIP
+   and X_s+1 = rk4_normalized(X_s, u_s, pf[b,s]) with u_s held over the four stages.  Within
+   the critical region of the solve's active set u_s is the QP's own optimum for the state
+   x_s.  The clip is the QP's input set (src/mpc_cvx_euler_3f.py:113-136, 2f), in this order:
+   torques to +-7.78, 7.78, 4; a swing leg (C0 == 0) gets f = 0; a stance leg fz to [0, 206],
+   then fx to +-mu_b fz and fy to +-mu_b fz (3f and CAS contexts) or to 0 (2f).
+     U      robot b's nominal input u*_0 at U[b*U_bstride .. +6)
+     K      its row-major [6][12] gain at K[b*K_bstride .. +72) (K_bstride = 72 for the S
+            [B,1,6,12] of hmpc_sens_batch with n_stages = 1)
+     x_nom  rows 0 and 1 at x_nom[b*xnom_bstride .. +24) (xnom_bstride = 12 (N+1) for x*
+            itself; row 1 is read only with HMPC_FB_INTERP)
+     pf     as in hmpc_plant_batch
+     C0     the period's contact flag at C0[b*C0_bstride] (the first entry of the solve's C
+            row), or NULL = stance
+     mu     [B] or NULL = the context's
+   Outputs: X in place; X_hist [B,n_steps,13], U_hist [B,n_steps,6] (the applied inputs),
+   x_out [B,12] = convert(X) after the last step and sat [B] (the number of steps in which
+   the clip moved a component by more than 1e-8 (1 + |bound|), the rule of hmpc_kkt_batch's
+   act_tol; 0 without HMPC_FB_CLIP) may each be NULL.  J is a host pointer.  HMPC_ERR_ARG for
+   a null X, U, K, x_nom, pf or J, n_steps < 1, stage_steps < 1, an unknown flag bit, a
+   negative stride or dt <= 0.  Serves every context, like hmpc_plant_batch.  Asynchronous,
+   allocates nothing (can be captured into a HIP graph). */
+#define HMPC_FB_CLIP   1
+#define HMPC_FB_INTERP 2
+int hmpc_plant_fb_batch(hmpc_ctx* ctx, int64_t B, int n_steps, int stage_steps, double dt,
+                        const double* J, double* X,
+                        const double* U, int64_t U_bstride,
+                        const double* K, int64_t K_bstride,
+                        const double* x_nom, int64_t xnom_bstride,
+                        const double* pf, int64_t pf_bstride, int64_t pf_sstride,
+                        const double* C0, int64_t C0_bstride,
+                        const double* mu, int flags,
+                        double* X_hist, double* U_hist, double* x_out, int32_t* sat, void* stream);
 
 /* Runner.path_plan_init (src/robotrunner.py:182-226) for B robots on the
    device: robot b's plan from its own start x_in[b] and goal xf[b] (convert()ed
