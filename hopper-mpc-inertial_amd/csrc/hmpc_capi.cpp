@@ -12,9 +12,11 @@
 #include <string.h>
 
 #include <string>
+#include <vector>
 
 #include "../../include/hmpc.h"
 #include "hmpc_internal.h"
+#include "hmpc_model.h"
 
 struct hmpc_ctx {
   int variant;
@@ -72,6 +74,7 @@ struct hmpc_ctx {
   // planner scratch (footstep counter, peak lists)
   void* plan_scratch = nullptr;
   int64_t plan_scratch_bytes = 0;
+  double* ctg_tab = nullptr;   // [N][12] constant blocks of the cost-to-go, then [3][N(N+1)/2] (hmpc::ctg_table, hess_table)
   hipStream_t own_stream = nullptr;
   // cross-stream ordering: the workspaces and self-resetting counters above
   // are per context, so a solve issued on another stream than the last one
@@ -80,6 +83,46 @@ struct hmpc_ctx {
   hipStream_t last_stream = nullptr;
   bool has_last = false;
 };
+
+namespace hmpc {
+
+void ctg_table(int N, double dt, double* out) {
+  const int pos[4] = {0, 1, 2, 5}, vel[4] = {6, 7, 8, 11};
+  for (int q = 0; q < 4; ++q) {
+    // [[a, b], [b, c]] with p' = p + dt v, then + Q (diagonal); S_N = kTermQ Q
+    double ta = kTermQ * kQ[pos[q]], tb = 0.0, tc = kTermQ * kQ[vel[q]];
+    for (int t = N; t >= 1; --t) {
+      double* o = out + 12 * (t - 1) + 3 * q;
+      o[0] = ta; o[1] = tb; o[2] = tc;
+      const double aa = ta, bb = tb, cc = tc;
+      tb = fma(dt, aa, bb);
+      tc = cc + dt * (2.0 * bb + dt * aa);
+      ta = aa + kQ[pos[q]];
+      tc = tc + kQ[vel[q]];
+    }
+  }
+}
+
+void hess_table(int N, double dt, double m, double* out) {
+  const int NP = N * (N + 1) / 2;
+  const double dtm = dt / m;
+  double* blocks = new double[12 * (size_t)N];
+  ctg_table(N, dt, blocks);
+  for (int a = 0; a < 3; ++a)
+    for (int i = 0; i < N; ++i) {
+      // b = Bd_i e_a has dt/m in row v_a; f = S_{i+1} b; g_j = Ad' g_{j+1}
+      // (v += dt p); H = 2 Bd_j[:, a]' g_j -- as phase 3 did per instance
+      const double gp = blocks[12 * i + 3 * a + 1] * dtm;
+      double gv = blocks[12 * i + 3 * a + 2] * dtm;
+      for (int j = i; j >= 0; --j) {
+        out[a * NP + i * (i + 1) / 2 + j] = 2.0 * (dtm * gv);
+        gv = fma(dt, gp, gv);
+      }
+    }
+  delete[] blocks;
+}
+
+}  // namespace hmpc
 
 namespace {
 
@@ -122,6 +165,7 @@ hmpc::SolveArgs make_args(hmpc_ctx* c, int64_t B, const double* x_in, const doub
   a.split_stream = nullptr; a.split_fork = nullptr; a.split_join = nullptr;
   a.precision = c->precision;
   a.refine = c->refine;
+  a.ctg_tab = c->ctg_tab;
   return a;
 }
 
@@ -533,7 +577,40 @@ int hmpc_create(hmpc_ctx** out, int variant, int N, double t, double m, double g
   memcpy(c->Jinv, Jinv, sizeof(c->Jinv));
   memcpy(c->rh, rh, sizeof(c->rh));
   c->uref_mode = uref_mode;
+  // the per-context tables: they depend on (t, m, N) and the model's constants
+  // only, so they are built once, here: [N][12] blocks, then [3][N(N+1)/2]
+  {
+    const size_t nb = 12 * (size_t)N, nh = 3 * (size_t)N * (size_t)(N + 1) / 2;
+    std::vector<double> tab(nb + nh);
+    hmpc::ctg_table(N, t, tab.data());
+    hmpc::hess_table(N, t, m, tab.data() + nb);
+    if (hipSetDevice(device) != hipSuccess) {
+      delete c;
+      return HMPC_ERR_HIP;
+    }
+    if (hipMalloc(&c->ctg_tab, sizeof(double) * tab.size()) != hipSuccess) {
+      delete c;
+      return HMPC_ERR_NOMEM;
+    }
+    if (hipMemcpy(c->ctg_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(c->ctg_tab);
+      delete c;
+      return HMPC_ERR_HIP;
+    }
+  }
   *out = c;
+  return HMPC_OK;
+}
+
+int hmpc_hess_table(int N, double t, double m, double* out) {
+  if (N <= 0 || !(t > 0.0) || !(m > 0.0) || !out) return HMPC_ERR_ARG;
+  hmpc::hess_table(N, t, m, out);
+  return HMPC_OK;
+}
+
+int hmpc_ctg_table(int N, double t, double* out) {
+  if (N <= 0 || !(t > 0.0) || !out) return HMPC_ERR_ARG;
+  hmpc::ctg_table(N, t, out);
   return HMPC_OK;
 }
 
@@ -553,6 +630,7 @@ int hmpc_destroy(hmpc_ctx* c) {
   if (c->kws) (void)hipFree(c->kws);
   if (c->kinst) (void)hipFree(c->kinst);
   if (c->plan_scratch) (void)hipFree(c->plan_scratch);
+  if (c->ctg_tab) (void)hipFree(c->ctg_tab);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   if (c->last_ev) (void)hipEventDestroy(c->last_ev);
   delete c;

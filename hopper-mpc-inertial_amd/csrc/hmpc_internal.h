@@ -101,7 +101,21 @@ struct SolveArgs {
   // both classes on the caller's stream, one after the other
   hipStream_t split_stream;
   hipEvent_t split_fork, split_join;
+  // the context's tables: [N][12], the blocks of S_t that do not depend on the
+  // instance (ctg_table), then [3][N(N+1)/2], the translational part of the 3f
+  // condensed Hessian (hess_table); read by the dense kernels in phase 0
+  const double* ctg_tab;
 };
+
+// The instance-independent 2x2 blocks of the cost-to-go S_t, t = 1..N (row
+// t - 1): [pp, pv, vv] of the three translational axes, then [tt, tw, ww] of
+// yaw -- entries 0..11 of the dense kernels' S_t (hmpc_model.h).  fp64, in the
+// operation order of the recursion the kernels ran per instance before.
+void ctg_table(int N, double dt, double* out);
+// The translational part of the 3f condensed Hessian, H[(i, a), (j, a)] through
+// (p_a, v_a), a = x, y, z: three lower triangles [3][N(N+1)/2], row i at
+// i(i+1)/2.  It follows ctg_table's blocks in the context's device table.
+void hess_table(int N, double dt, double m, double* out);
 
 // The Riccati kernel (hmpc_ric.hip): any horizon 1 <= N <= kRicNmax, one
 // wavefront per instance.

@@ -14,7 +14,8 @@
 //      and the backward cost-to-go S_t = W_{t-1} + Ad_t' S_{t+1} Ad_t.
 //      S_t is block-structured (Ad never mixes translation and rotation and
 //      Q is diagonal): 3 x (p_a, v_a) 2x2 + (yaw, w_z) 2x2 + (roll, pitch,
-//      w_x, w_y) 4x4 = 22 unique entries.
+//      w_x, w_y) 4x4.  The 2x2 blocks do not depend on the instance; the 4x4
+//      is isotropic in the roll/pitch plane and carried as four scalars.
 //   3  lane v builds row v of the condensed Hessian (lower triangle: all the
 //      Cholesky reads) and its gradient entry: the impulse response
 //      e_j = Phi(j+1,i+1) B_i e_c (gradient), the diagonal block from
@@ -282,7 +283,7 @@ struct Lay {
   // seen over 65536 random N=10 instances is 12
   static constexpr int QMAX = QM > 0 ? QM : (NV < 20 ? NV : (N <= 10 ? 20 : 48));
   static constexpr int e2(int n) { return (n + 1) & ~1; }
-  static constexpr int NS = 22;                    // unique entries of S_t
+  static constexpr int NS = 16;                    // stored entries of S_t (15, padded)
   static constexpr int LCN = NV * (NV + 1) / 2;    // packed L
   // persistent
   static constexpr int XIN = 0;                    // [12]
@@ -305,13 +306,21 @@ struct Lay {
   static constexpr int GS = RM + e2(QMAX * (QMAX + 1) / 2);   // [W][QMAX] Gram-Schmidt partials (W > 1)
   static constexpr int GEND = GS + (W > 1 ? W * QMAX : 0);
   static constexpr int COLB = G0;                  // [2][NT+8] (phase 4 only), 16-B aligned
+  // phases 0-3, one wave: the context's translational Hessian tables
+  // [3][NP] (lower triangles, row i at i(i+1)/2) sit in the active-set state's
+  // space behind phase 3's 64 dump slots, where that space holds them (HTFIT:
+  // the full class; the compacted class's capacity-13 state does not, and its
+  // LDS block has no room to grow at 3 waves / SIMD)
+  static constexpr int NP = N * (N + 1) / 2;
+  static constexpr int HT = G0 + 64;
+  static constexpr bool HTFIT = W == 1 && GEND - HT >= 3 * NP;
   static_assert((G0 & 1) == 0, "column buffers must be 16-B aligned");
   static constexpr int U0 = (GEND > COLB + 2 * (NT + 8)) ? GEND : COLB + 2 * (NT + 8);
   // union A (phases 0-3)
   static constexpr int XLIN = U0;                  // [N][12]  rows 0..N-1
   static constexpr int PF = XLIN + 12 * N;         // [N][3]
   static constexpr int XREF = PF + e2(3 * N);      // [N][12]
-  static constexpr int SS = XREF + 12 * N;         // [N][22]  S_{t}, t = 1..N
+  static constexpr int SS = XREF + 12 * N;         // [N][NS]  S_{t}, t = 1..N
   static constexpr int DG = SS + NS * N;           // [N][12]  d_t, t = 1..N
   static constexpr int AJ = DG + 12 * N;           // [N][6]   adjoint a_t rows 6..11, t = 1..N
   static constexpr int ENDA = AJ + 6 * N;
@@ -559,9 +568,21 @@ __device__ __forceinline__ real tri_bwd(real acc, const real* Mc, const real* ze
 // product build compiles these to nothing.
 #ifdef HMPC_STAMPS
 #define HMPC_STAMP(i) (stamp_[i] = __builtin_amdgcn_s_memtime())
+#ifdef HMPC_STAMPS_P23
+// -DHMPC_STAMPS_P23: slots 9..11 time parts of phases 2 and 3 instead (the
+// cost-to-go recursion, f = S b, the adjoint's propagation); the values that
+// enter and leave a timed part are pinned so it is not scheduled across its
+// stamps (HMPC_PIN23).  The active set's timers are off in this build.
+#define HMPC_TIC(v) ((void)0)
+#define HMPC_TOC(slot, v) ((void)0)
+#define HMPC_TIC23(v) const long long v = __builtin_amdgcn_s_memtime()
+#define HMPC_TOC23(slot, v) (stamp_[slot] += __builtin_amdgcn_s_memtime() - (v))
+#define HMPC_PIN23(x) pin(x)
+#else
 // accumulated sub-phase timers of the active set (slots 9..14)
 #define HMPC_TIC(v) const long long v = __builtin_amdgcn_s_memtime()
 #define HMPC_TOC(slot, v) (stamp_[slot] += __builtin_amdgcn_s_memtime() - (v))
+#endif
 #elif defined(HMPC_MARKS)   // phase markers in the .s (register-pressure work)
 #define HMPC_STAMP(i) asm volatile(";@@PHASE " #i)
 #define HMPC_TIC(v) asm volatile(";@@TIC " #v)
@@ -572,6 +593,11 @@ __device__ __forceinline__ real tri_bwd(real acc, const real* Mc, const real* ze
 #if !defined(HMPC_STAMPS) && !defined(HMPC_MARKS)
 #define HMPC_TIC(v) ((void)0)
 #define HMPC_TOC(slot, v) ((void)0)
+#endif
+#ifndef HMPC_TIC23
+#define HMPC_TIC23(v) ((void)0)
+#define HMPC_TOC23(slot, v) ((void)0)
+#define HMPC_PIN23(x) ((void)0)
 #endif
 
 // issue priority of the chain-bound phases (the Cholesky through the active
@@ -630,9 +656,19 @@ solve_kernel(SolveArgs a) {
   real* xs = sm + L::XS;
 #ifdef HMPC_STAMPS
   long long stamp_[16] = {0};
+#ifdef HMPC_STAMPS_P23
+  stamp_[15] = 0x503233;   // marks the build for tools/phase_stamps.py ("P23")
+#endif
 #endif
   HMPC_STAMP(0);
   constexpr bool kCmpCls = NVM > 0 && NVM <= kCmp3W;   // the split's compacted class
+  // 3f force-force entries of H take their translational part (through p_a,
+  // v_a: Bd's force columns there are dt/m I, 3f :28, and those blocks of S
+  // are constant) from the context's tables; the adjoint of phase 3 then
+  // carries its rotational rows only
+  // (fp64 only: the fp32 full class, at 168 VGPRs for 3 waves / SIMD, goes
+  // over its register budget with the tables and stays on the old code)
+  constexpr bool kHessTab = VAR == 3 && L::HTFIT && !kF32;
   if constexpr (!kCmpCls) __builtin_amdgcn_s_setprio(kPrioFullBase);
 
   const int tid = threadIdx.x;
@@ -672,8 +708,15 @@ solve_kernel(SolveArgs a) {
     constexpr int NR = (12 * N + NT - 1) / NT, NP = (3 * N + NT - 1) / NT, NCC = (N + NT - 1) / NT;
     const double* xp = a.x_lin + b * 12 * (N + 1);
     const int mode = a.shift_mode;
-    real vi, vr[NR], vp[NP], vc[NCC], vl[NR];
+    real vi, vr[NR], vp[NP], vc[NCC], vl[NR], vt[NR];
     vi = a.x_in[b * 12 + (tid < 12 ? tid : 0)];
+    // the context's table of S_t's constant blocks (entries 0..11 of every
+    // S_t; fp64 in memory, converted here in the fp32 builds)
+    sfor<0, NR>([&](auto itc) __attribute__((always_inline)) {
+      constexpr int it = decltype(itc)::value;
+      const int i = tid + it * NT;
+      vt[it] = a.ctg_tab[i < 12 * N ? i : 0];
+    });
     sfor<0, NR>([&](auto itc) __attribute__((always_inline)) {
       constexpr int it = decltype(itc)::value;
       const int i = tid + it * NT, ic = i < 12 * N ? i : 0;
@@ -695,13 +738,27 @@ solve_kernel(SolveArgs a) {
       const int i = tid + it * NT;
       vc[it] = a.C[b * a.C_bs + (i < N ? i : 0)];
     });
+    // ... and its translational Hessian tables (phase 3), behind the blocks
+    constexpr int NH = kHessTab ? (3 * L::NP + NT - 1) / NT : 0;
+    real vh[NH > 0 ? NH : 1];
+    sfor<0, NH>([&](auto itc) __attribute__((always_inline)) {
+      constexpr int it = decltype(itc)::value;
+      const int i = tid + it * NT;
+      vh[it] = a.ctg_tab[12 * N + (i < 3 * L::NP ? i : 0)];
+    });
     const real mu_b = a.mu ? a.mu[b] : a.mu_default;
+    sfor<0, NH>([&](auto itc) __attribute__((always_inline)) {
+      constexpr int it = decltype(itc)::value;
+      const int i = tid + it * NT;
+      if (i < 3 * L::NP) sm[L::HT + i] = vh[it];
+    });
     if (tid < 12) sm[L::XIN + tid] = vi;
     if (tid == 0) sm[L::ZR + 1] = mu_b;   // read again in phase 6
     sfor<0, NR>([&](auto itc) __attribute__((always_inline)) {
       constexpr int it = decltype(itc)::value;
       const int i = tid + it * NT;
       if (i < 12 * N) {
+        sm[L::SS + L::NS * (i / 12) + (i - 12 * (i / 12))] = vt[it];
         sm[L::XREF + i] = vr[it];
         if (mode != 1) sm[L::XLIN + i] = (mode == 2 && i < 12) ? vi : vl[it];
       }
@@ -803,28 +860,30 @@ solve_kernel(SolveArgs a) {
     //   cost-to-go (wave-uniform) S_N = W_{N-1} = 100 Q, S_t = Q + Ad_t' S_{t+1} Ad_t
     real xr = tid < 12 ? sm[L::XIN + tid] : 0.0;
     const real qr = qdiag(tid);
-    // S_t entries 0..11 (translational axes and yaw) lane-parallel: lane
-    // q < 4 holds block q's [pp, pv, vv] (q = 3: yaw [tt, tw, ww]), one
-    // instruction stream for the four blocks.  These blocks do not depend on
-    // the instance; the roll/pitch block (entries 12..21, yaw-dependent) stays
-    // wave-uniform in s[].
-    const real qa = tid == 0 ? kQ[0] : tid == 1 ? kQ[1] : tid == 2 ? kQ[2] : kQ[5];
-    const real qc = tid == 0 ? kQ[6] : tid == 1 ? kQ[7] : tid == 2 ? kQ[8] : kQ[11];
-    real ta = kTermQ * qa, tb = 0.0, tc = kTermQ * qc;
-    real s[10];   // P00 P01 P11 M00 M01 M10 M11 Q00 Q01 Q11 (entries 12..21)
-    s[0] = kTermQ * kQ[3]; s[1] = 0.0; s[2] = kTermQ * kQ[4];
-    s[3] = s[4] = s[5] = s[6] = 0.0;
-    s[7] = kTermQ * kQ[9]; s[8] = 0.0; s[9] = kTermQ * kQ[10];
-    real* const tstore = sm + L::SS + 3 * (tid < 4 ? tid : 0);
+    // S_t entries 0..11 (translational axes and yaw) do not depend on the
+    // instance: phase 0 copied them from the context's table.
+    // The roll/pitch block y = (x3, x4, w_x, w_y) is isotropic in the plane:
+    // Q weighs roll like pitch and w_x like w_y, and Ad acts on y as
+    // theta' = theta + D w with D = dt [[c, s], [-s, c]], a scaled rotation.
+    // Write Z(x, y) = [[x, -y], [y, x]]; these matrices commute and
+    // Z(x1, y1)' Z(x2, y2) = Z(x1 x2 + y1 y2, x1 y2 - y1 x2).  With
+    // S = [[a I, Z(p, q)], [Z(p, q)', c I]] at t + 1 and D = Z(dp, dq),
+    // dp = dt cos psi_t, dq = -dt sin psi_t, the recursion
+    // S_t = Q + Ad_t' S_{t+1} Ad_t gives
+    //   Z(p, q) <- Z(p, q) + a D = Z(np, nq)          (a dt e^{-i psi} summed)
+    //   c I     <- c I + D' Z(np, nq) + Z(p, q)' D + Q_w
+    //            = (c + dp (np + p) + dq (nq + q) + Q_w) I  (the off-diagonal cancels)
+    //   a       <- a + Q_theta                         (the same for every instance)
+    // so the block is (a, p, q, c), from S_N = kTermQ Q: a, c on the diagonal,
+    // p = q = 0.  Phase 3 reads p, q, c (entries 12..14; s_times_rp).
+    static_assert(kQ[3] == kQ[4] && kQ[9] == kQ[10], "the roll/pitch block of S_t is isotropic only if Q is");
+    real ra = kTermQ * kQ[3], rp = 0.0, rq = 0.0, rc = kTermQ * kQ[9];
     auto store_s = [&](int t) __attribute__((always_inline)) {
-      if (tid < 4) {
-        tstore[22 * t] = ta;
-        tstore[22 * t + 1] = tb;
-        tstore[22 * t + 2] = tc;
+      if (tid == 0) {
+        sm[L::SS + L::NS * t + 12] = rp;
+        sm[L::SS + L::NS * t + 13] = rq;
+        sm[L::SS + L::NS * t + 14] = rc;
       }
-      if (tid == 0)
-#pragma unroll
-        for (int e = 0; e < 10; ++e) sm[L::SS + 22 * t + 12 + e] = s[e];
     };
     if (tid == 2) sm[L::ZB] = xr;
     store_s(N - 1);
@@ -848,34 +907,21 @@ solve_kernel(SolveArgs a) {
       if (tid == 2) sm[L::ZB + k + 1] = xr;
       constexpr int t = N - 1 - k;
       if constexpr (t >= 1) {
+        HMPC_TIC23(t_ctg);
+        HMPC_PIN23(ra); HMPC_PIN23(rp); HMPC_PIN23(rq); HMPC_PIN23(rc);
         const real ct = rdlane(cpl, t), st = rdlane(spl, t);
-        // translational axes and yaw: [[a, b], [b, c]] with p' = p + dt v,
-        // then + W_{t-1} = Q (diagonal)
+        // roll/pitch block (a, p, q, c), see above
         {
-          const real aa = ta, bb = tb, cc = tc;
-          tb = fma(dt, aa, bb);
-          tc = cc + dt * (real(2) * bb + dt * aa);
-          ta = aa + qa;
-          tc = tc + qc;
+          const real dp = ct * dt, dq = -(st * dt);
+          const real np = fma(ra, dp, rp), nq = fma(ra, dq, rq);
+          rc += dp * (np + rp) + dq * (nq + rq);
+          rc += real(kQ[9]);
+          rp = np;
+          rq = nq;
+          ra += real(kQ[3]);
         }
-        // roll/pitch block, theta' = theta + D w with D = dt [[c, s], [-s, c]]:
-        //   M' = M + P D,   Qm' = Qm + D'(M + P D) + M' D   (old M in the last term)
-        const real D00 = ct * dt, D01 = st * dt, D10 = -st * dt, D11 = ct * dt;
-        const real P00 = s[0], P01 = s[1], P11 = s[2];
-        const real M00 = s[3], M01 = s[4], M10 = s[5], M11 = s[6];
-        const real N00 = M00 + (P00 * D00 + P01 * D10), N01 = M01 + (P00 * D01 + P01 * D11);
-        const real N10 = M10 + (P01 * D00 + P11 * D10), N11 = M11 + (P01 * D01 + P11 * D11);
-        const real A00 = D00 * N00 + D10 * N10, A01 = D00 * N01 + D10 * N11;
-        const real A11 = D01 * N01 + D11 * N11;
-        const real B00 = M00 * D00 + M10 * D10, B01 = M00 * D01 + M10 * D11;
-        const real B11 = M01 * D01 + M11 * D11;
-        s[7] += A00 + B00;
-        s[8] += A01 + B01;
-        s[9] += A11 + B11;
-        s[3] = N00; s[4] = N01; s[5] = N10; s[6] = N11;
-        s[0] += kQ[3]; s[2] += kQ[4];
-        s[7] += kQ[9]; s[9] += kQ[10];
         store_s(t - 1);
+        HMPC_TOC23(9, t_ctg);
       }
     });
     B::sync();
@@ -959,7 +1005,11 @@ solve_kernel(SolveArgs a) {
     for (int r = 0; r < 3; ++r) e0[6 + r] = ci < 3 ? rowm * bv<VAR>(r, ci, dtm, cpi, spi) : 0.0;
 #pragma unroll
     for (int r = 0; r < 3; ++r) e0[9 + r] = rowm * bwi[6 * r + ci];
-    s_times<true>(sm + L::SS + 22 * ii, e0, f);
+    HMPC_TIC23(t_sb);
+    sfor<6, 12>([&](auto rc) __attribute__((always_inline)) { HMPC_PIN23(e0[decltype(rc)::value]); });
+    s_times_rp(sm + L::SS + L::NS * ii, e0, f);
+    sfor<0, 12>([&](auto rc) __attribute__((always_inline)) { HMPC_PIN23(f[decltype(rc)::value]); });
+    HMPC_TOC23(10, t_sb);
     // gradient: h_v = 2 b' a_{i+1} (b = Bd_i e_c, a = adjoint of phase 2)
     real hacc = 0.0;
 #pragma unroll
@@ -976,12 +1026,16 @@ solve_kernel(SolveArgs a) {
       constexpr int j = decltype(jc)::value;
       if constexpr (j < N - 1) {
         const real cp1 = smj[L::CS + 2 * (j + 1)], sp1 = smj[L::CS + 2 * (j + 1) + 1];
+        HMPC_TIC23(t_adv);
+        sfor<0, 12>([&](auto rc) __attribute__((always_inline)) { HMPC_PIN23(g[decltype(rc)::value]); });
         real gn[12];
 #pragma unroll
         for (int r = 0; r < 12; ++r) gn[r] = g[r];
         adt_times(gn, dt, cp1, sp1);
 #pragma unroll
         for (int r = 0; r < 12; ++r) g[r] = (ii > j) ? gn[r] : g[r];
+        sfor<0, 12>([&](auto rc) __attribute__((always_inline)) { HMPC_PIN23(g[decltype(rc)::value]); });
+        HMPC_TOC23(11, t_adv);
       }
     };
     if constexpr (W == 1) {
@@ -999,6 +1053,12 @@ solve_kernel(SolveArgs a) {
       xs[tid] = 0.0;
       B::sync();   // every lane's S / adjoint reads are issued before the first H store
       real cp_up = 0.0, sp_up = 0.0;   // cos / sin of the stage above (advance)
+      // my force's row of its axis' table (entries right of the diagonal: any
+      // in-range value) and which force column takes it
+      const unsigned tba = lds_addr(sm + L::HT + (ci < 3 ? ci : 0) * L::NP + ((ii * (ii + 1)) >> 1));
+      real mc[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) mc[c] = ci == c ? rowm : real(0);
       sfor<0, N>([&](auto jc) __attribute__((always_inline)) {
         constexpr int j = N - 1 - decltype(jc)::value;
         // stage j's rows 9..11 of Bd and cos / sin in one LDS round trip (ten
@@ -1006,6 +1066,7 @@ solve_kernel(SolveArgs a) {
         // next to its product and waits for it there, three round trips per
         // entry of H in series
         real2 bwp[9], csp;
+        real tv = 0.0;   // H[(ii, ci), (j, ci)]'s translational part (kHessTab)
         {
           const unsigned sb = lds_addr(sm + opaque_zero());
           sfor<0, 9>([&](auto ic) __attribute__((always_inline)) {
@@ -1013,9 +1074,11 @@ solve_kernel(SolveArgs a) {
             lds_ld2<RB * (L::BW + 18 * j + 2 * i)>(bwp[i], sb);
           });
           lds_ld2<RB * (L::CS + 2 * j)>(csp, sb);
+          if constexpr (kHessTab) lds_ld1(tv, tba + (unsigned)(RB * j));
           lds_wait<0>(bwp[0], bwp[1], bwp[2], bwp[3]);
           lds_wait<0>(bwp[4], bwp[5], bwp[6], bwp[7]);
           lds_wait<0>(bwp[8], csp);
+          if constexpr (kHessTab) lds_wait<0>(tv);
         }
         real bw[18];
 #pragma unroll
@@ -1024,12 +1087,17 @@ solve_kernel(SolveArgs a) {
           bw[2 * i + 1] = bwp[i].y;
         }
         if constexpr (j < N - 1) {   // g -> g_j = Ad_{j+1}' g_{j+1} (as advance())
+          HMPC_TIC23(t_adv);
+          sfor<0, 12>([&](auto rc) __attribute__((always_inline)) { HMPC_PIN23(g[decltype(rc)::value]); });
           real gn[12];
 #pragma unroll
           for (int r = 0; r < 12; ++r) gn[r] = g[r];
-          adt_times(gn, dt, cp_up, sp_up);
+          if constexpr (kHessTab) adt_times_rot(gn, dt, cp_up, sp_up);
+          else adt_times(gn, dt, cp_up, sp_up);
 #pragma unroll
           for (int r = 0; r < 12; ++r) g[r] = (ii > j) ? gn[r] : g[r];
+          sfor<0, 12>([&](auto rc) __attribute__((always_inline)) { HMPC_PIN23(g[decltype(rc)::value]); });
+          HMPC_TOC23(11, t_adv);
         }
         const real cp = csp.x, sp = csp.y;
         cp_up = cp;
@@ -1043,7 +1111,9 @@ solve_kernel(SolveArgs a) {
         if (st) {   // the stance forces (2f: fx, fz)
           sfor<0, 3>([&](auto c2c) __attribute__((always_inline)) {
             constexpr int c2 = decltype(c2c)::value;
-            if constexpr (!(VAR == 2 && c2 == 1))
+            if constexpr (kHessTab)
+              put(o + c2, fma(mc[c2], tv, bd_dot_rot(c2, g, bw)));
+            else if constexpr (!(VAR == 2 && c2 == 1))
               put(o + (VAR == 3 ? c2 : (c2 == 0 ? 0 : 1)), bd_dot<VAR>(c2, g, bw, dtm, cp, sp));
           });
         }

@@ -176,6 +176,27 @@ __device__ __forceinline__ void s_times(const R* s, const R (&e)[12], R (&f)[12]
   f[10] = M01 * e[3] + M11 * e[4] + Q01 * e[9] + Q11 * e[10];
 }
 
+// f = S b for an input impulse b (b[0..5] = 0) and the dense kernels' S_t:
+// entries 0..11 as above, then the isotropic roll/pitch block as (p, q, c)
+// at 12..14 -- S[theta][w] = [[p, -q], [q, p]], S[w][w] = c I (derivation in
+// hmpc_kernels.hip, phase 2).  The block's S[theta][theta] = a I meets only
+// zeros of b.
+template <typename R>
+__device__ __forceinline__ void s_times_rp(const R* s, const R (&e)[12], R (&f)[12]) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    f[a] = s[3 * a + 1] * e[6 + a];
+    f[6 + a] = s[3 * a + 2] * e[6 + a];
+  }
+  f[5] = s[10] * e[11];
+  f[11] = s[11] * e[11];
+  const R p = s[12], q = s[13], c = s[14];
+  f[3] = p * e[9] - q * e[10];
+  f[4] = q * e[9] + p * e[10];
+  f[9] = c * e[9];
+  f[10] = c * e[10];
+}
+
 // x <- Ad x with Ad = I + dt A(psi): p += dt v; theta += dt Rz(psi) w
 // (src/mpc_cvx_euler_3f.py:27,87,91; rz of src/utils.py:46-51)
 template <typename R>
@@ -192,6 +213,16 @@ template <typename R>
 __device__ __forceinline__ void adt_times(R (&g)[12], R dt, R cp, R sp) {
 #pragma unroll
   for (int a = 0; a < 3; ++a) g[6 + a] = fma(dt, g[a], g[6 + a]);
+  const R g3 = g[3], g4 = g[4];
+  g[9] = g[9] + ((cp * dt) * g3 + (-sp * dt) * g4);
+  g[10] = g[10] + ((sp * dt) * g3 + (cp * dt) * g4);
+  g[11] = fma(dt, g[5], g[11]);
+}
+
+// g <- Ad' g on the rotational rows alone (g[0..2], g[6..8] not carried: the
+// translational part of H comes from the context's tables)
+template <typename R>
+__device__ __forceinline__ void adt_times_rot(R (&g)[12], R dt, R cp, R sp) {
   const R g3 = g[3], g4 = g[4];
   g[9] = g[9] + ((cp * dt) * g3 + (-sp * dt) * g4);
   g[10] = g[10] + ((sp * dt) * g3 + (cp * dt) * g4);
@@ -283,6 +314,15 @@ __device__ __forceinline__ R bd_dot(int c2, const R (&y)[12], const R* bw, R dtm
   }
 #pragma unroll
   for (int r = 0; r < 3; ++r) acc = fma(bw[6 * r + c2], y[9 + r], acc);
+  return R(2) * acc;
+}
+
+// the rotational part of bd_dot: 2 Bd_j[9..11, c2]' y[9..11]
+template <typename R>
+__device__ __forceinline__ R bd_dot_rot(int c2, const R (&y)[12], const R* bw) {
+  R acc = bw[c2] * y[9];
+  acc = fma(bw[6 + c2], y[10], acc);
+  acc = fma(bw[12 + c2], y[11], acc);
   return R(2) * acc;
 }
 

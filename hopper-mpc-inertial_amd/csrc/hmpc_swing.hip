@@ -239,8 +239,9 @@ struct SwLay {
   static constexpr int U0 = GEND > COLB + 2 * CBS ? GEND : COLB + 2 * CBS;
   // union A (phases 0-3)
   static constexpr int XREF = U0;                // [N][12]
-  static constexpr int SS = XREF + 12 * N;       // [N][9] S_{t+1}: tw ww M00 M01 M10 M11 Q00 Q01 Q11
-  static constexpr int AJ = SS + 9 * N;          // [N][3] adjoint a_{t+1}, rows 9..11
+  static constexpr int NS = 6;                   // stored entries of S_t (5, padded)
+  static constexpr int SS = XREF + 12 * N;       // [N][NS] S_{t+1}: tw ww p q c (roll/pitch block: phase 2)
+  static constexpr int AJ = SS + NS * N;         // [N][3] adjoint a_{t+1}, rows 9..11
   static constexpr int ENDA = AJ + 3 * N;
   // union B (phases 4-7)
   static constexpr int LC = U0;                  // M = L diag(L)^-1, column-major packed, 1/L_kk on the diagonal
@@ -395,12 +396,28 @@ constexpr int kPrioSwing = 1;
 // its stamps.
 #ifdef HMPC_STAMPS
 #define SW_STAMP(i) (stamp_[i] = __builtin_amdgcn_s_memtime())
+#ifdef HMPC_STAMPS_P23
+// -DHMPC_STAMPS_P23: slot 9 times the cost-to-go recursion of phase 2 and
+// slot 11 the adjoint's propagation in phase 3 instead (as the dense kernel's
+// build of that name); the active set's timers are off
+#define SW_TIC(v) ((void)0)
+#define SW_TOC(slot, v) ((void)0)
+#define SW_TIC23(v) const long long v = __builtin_amdgcn_s_memtime()
+#define SW_TOC23(slot, v) (stamp_[slot] += __builtin_amdgcn_s_memtime() - (v))
+#define SW_PIN23(x) pin(x)
+#else
 #define SW_TIC(v) const long long v = __builtin_amdgcn_s_memtime()
 #define SW_TOC(slot, v) (stamp_[slot] += __builtin_amdgcn_s_memtime() - (v))
+#endif
 #else
 #define SW_STAMP(i) ((void)0)
 #define SW_TIC(v) ((void)0)
 #define SW_TOC(slot, v) ((void)0)
+#endif
+#ifndef SW_TIC23
+#define SW_TIC23(v) ((void)0)
+#define SW_TOC23(slot, v) ((void)0)
+#define SW_PIN23(x) ((void)0)
 #endif
 
 // ---------------------------------------------------------------------------
@@ -426,6 +443,9 @@ __global__ void __launch_bounds__(64, HMPC_SWING_WAVES) swing_kernel(SolveArgs a
   const double dt = a.dt;
 #ifdef HMPC_STAMPS
   long long stamp_[16] = {0};
+#ifdef HMPC_STAMPS_P23
+  stamp_[15] = 0x503233;   // marks the build for tools/phase_stamps.py ("P23")
+#endif
 #endif
   SW_STAMP(0);
 
@@ -509,16 +529,16 @@ __global__ void __launch_bounds__(64, HMPC_SWING_WAVES) swing_kernel(SolveArgs a
     bool zbad0 = hl == 2 && xr - kZmin < -kTol, zbad1 = false;
     // yaw block [tt, tw, ww] of S (x5, w_z): no yaw dependence
     double ya = kTermQ * kQ[5], yb = 0.0, yc = kTermQ * kQ[11];
-    double s[10];   // P00 P01 P11 M00 M01 M10 M11 Q00 Q01 Q11 (roll/pitch block)
-    s[0] = kTermQ * kQ[3]; s[1] = 0.0; s[2] = kTermQ * kQ[4];
-    s[3] = s[4] = s[5] = s[6] = 0.0;
-    s[7] = kTermQ * kQ[9]; s[8] = 0.0; s[9] = kTermQ * kQ[10];
+    // roll/pitch block (x3, x4, w_x, w_y) of S as (a, p, q, c): S[theta][theta]
+    // = a I, S[theta][w] = [[p, -q], [q, p]], S[w][w] = c I (isotropic in the
+    // plane; the derivation is in hmpc_kernels.hip, phase 2)
+    static_assert(kQ[3] == kQ[4] && kQ[9] == kQ[10], "the roll/pitch block of S_t is isotropic only if Q is");
+    double ra = kTermQ * kQ[3], rp = 0.0, rq = 0.0, rc = kTermQ * kQ[9];
     auto store_s = [&](int t) __attribute__((always_inline)) {
       if (hl == 0) {
-        double* st = sm + L::SS + 9 * t;
+        double* st = sm + L::SS + L::NS * t;
         st[0] = yb; st[1] = yc;
-#pragma unroll
-        for (int e = 0; e < 7; ++e) st[2 + e] = s[3 + e];
+        st[2] = rp; st[3] = rq; st[4] = rc;
       }
     };
     store_s(N - 1);
@@ -536,6 +556,9 @@ __global__ void __launch_bounds__(64, HMPC_SWING_WAVES) swing_kernel(SolveArgs a
       else if constexpr (k + 1 <= N - 1) zbad1 = zbad1 || (hl == 2 && xr - kZmin < -kTol);
       constexpr int t = N - 1 - k;
       if constexpr (t >= 1) {
+        SW_TIC23(t_ctg);
+        SW_PIN23(ya); SW_PIN23(yb); SW_PIN23(yc);
+        SW_PIN23(ra); SW_PIN23(rp); SW_PIN23(rq); SW_PIN23(rc);
         const double ct = rbc<t>(cpl), st = rbc<t>(spl);
         {
           const double aa = ya, bb = yb, cc = yc;
@@ -544,22 +567,17 @@ __global__ void __launch_bounds__(64, HMPC_SWING_WAVES) swing_kernel(SolveArgs a
           ya = aa + kQ[5];
           yc = yc + kQ[11];
         }
-        const double D00 = ct * dt, D01 = st * dt, D10 = -st * dt, D11 = ct * dt;
-        const double P00 = s[0], P01 = s[1], P11 = s[2];
-        const double M00 = s[3], M01 = s[4], M10 = s[5], M11 = s[6];
-        const double N00 = M00 + (P00 * D00 + P01 * D10), N01 = M01 + (P00 * D01 + P01 * D11);
-        const double N10 = M10 + (P01 * D00 + P11 * D10), N11 = M11 + (P01 * D01 + P11 * D11);
-        const double A00 = D00 * N00 + D10 * N10, A01 = D00 * N01 + D10 * N11;
-        const double A11 = D01 * N01 + D11 * N11;
-        const double B00 = M00 * D00 + M10 * D10, B01 = M00 * D01 + M10 * D11;
-        const double B11 = M01 * D01 + M11 * D11;
-        s[7] += A00 + B00;
-        s[8] += A01 + B01;
-        s[9] += A11 + B11;
-        s[3] = N00; s[4] = N01; s[5] = N10; s[6] = N11;
-        s[0] += kQ[3]; s[2] += kQ[4];
-        s[7] += kQ[9]; s[9] += kQ[10];
+        {
+          const double dp = ct * dt, dq = -(st * dt);
+          const double np = fma(ra, dp, rp), nq = fma(ra, dq, rq);
+          rc += dp * (np + rp) + dq * (nq + rq);
+          rc += kQ[9];
+          rp = np;
+          rq = nq;
+          ra += kQ[3];
+        }
         store_s(t - 1);
+        SW_TOC23(9, t_ctg);
       }
     });
     // adjoint a_N = d_N, a_t = d_t + Ad_t' a_{t+1}; rows 9..11 (the torque
@@ -589,12 +607,11 @@ __global__ void __launch_bounds__(64, HMPC_SWING_WAVES) swing_kernel(SolveArgs a
     const double rowm = active_lane ? 1.0 : 0.0;
     const double* bwi = sm + L::BW + 9 * ii;
     const double e9 = rowm * bwi[ci], e10 = rowm * bwi[3 + ci], e11 = rowm * bwi[6 + ci];
-    const double* si = sm + L::SS + 9 * ii;   // S_{i+1}
-    const double tw = si[0], ww = si[1], M00 = si[2], M01 = si[3], M10 = si[4], M11 = si[5];
-    const double Q00 = si[6], Q01 = si[7], Q11 = si[8];
-    // f = S_{i+1} b, b = Bd_i e_c (rows 9..11; hmpc_model.h s_times<true>)
-    const double f3 = M00 * e9 + M01 * e10, f4 = M10 * e9 + M11 * e10, f5 = tw * e11;
-    double g9 = Q00 * e9 + Q01 * e10, g10 = Q01 * e9 + Q11 * e10, g11 = ww * e11;
+    const double* si = sm + L::SS + L::NS * ii;   // S_{i+1}
+    const double tw = si[0], ww = si[1], rp = si[2], rq = si[3], rc = si[4];
+    // f = S_{i+1} b, b = Bd_i e_c (rows 9..11; hmpc_model.h s_times_rp)
+    const double f3 = rp * e9 - rq * e10, f4 = rq * e9 + rp * e10, f5 = tw * e11;
+    double g9 = rc * e9, g10 = rc * e10, g11 = ww * e11;
     // gradient h_v = 2 b' a_{i+1}
     const double* aj = sm + L::AJ + 3 * ii;
     double hacc = 0.0;
@@ -625,6 +642,8 @@ __global__ void __launch_bounds__(64, HMPC_SWING_WAVES) swing_kernel(SolveArgs a
         lds_wait<0>(sj);
       }
       if constexpr (j < N - 1) {
+        SW_TIC23(t_adv);
+        SW_PIN23(g9); SW_PIN23(g10); SW_PIN23(g11);
         const double cp1 = cp_up, sp1 = sp_up;
         const double n9 = g9 + ((cp1 * dt) * f3 + (-sp1 * dt) * f4);
         const double n10 = g10 + ((sp1 * dt) * f3 + (cp1 * dt) * f4);
@@ -632,6 +651,8 @@ __global__ void __launch_bounds__(64, HMPC_SWING_WAVES) swing_kernel(SolveArgs a
         g9 = (ii > j) ? n9 : g9;
         g10 = (ii > j) ? n10 : g10;
         g11 = (ii > j) ? n11 : g11;
+        SW_PIN23(g9); SW_PIN23(g10); SW_PIN23(g11);
+        SW_TOC23(11, t_adv);
       }
       cp_up = cj;
       sp_up = sj;

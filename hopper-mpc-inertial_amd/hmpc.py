@@ -39,6 +39,8 @@ SIGNATURES = {
     'hmpc_create': (ctypes.c_int, [ctypes.POINTER(_VP), ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                    ctypes.c_double, ctypes.c_double, ctypes.c_double, _D, _D,
                                    ctypes.c_int, ctypes.c_int]),
+    'hmpc_ctg_table': (ctypes.c_int, [ctypes.c_int, ctypes.c_double, _D]),
+    'hmpc_hess_table': (ctypes.c_int, [ctypes.c_int, ctypes.c_double, ctypes.c_double, _D]),
     'hmpc_destroy': (ctypes.c_int, [_VP]),
     'hmpc_solve_batch': (ctypes.c_int, [_VP, ctypes.c_int64] + [_VP] * 11 + [_VP]),
     'hmpc_solve_batch_stats': (ctypes.c_int, [_VP, ctypes.c_int64] + [_VP] * 12 + [_VP]),

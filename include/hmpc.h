@@ -154,6 +154,17 @@ int hmpc_create(hmpc_ctx** out, int variant, int N, double t, double m, double g
                 double mu, const double* Jinv, const double* rh, int uref_mode,
                 int device);
 
+/* The part of the cost-to-go S_t (t = 1..N, row t - 1) that does not depend on
+ * the instance, as the context builds it once at creation for its kernels:
+ * out[N][12] = [pp, pv, vv] of the x, y, z axes, then [tt, tw, ww] of yaw.
+ * Host only. */
+int hmpc_ctg_table(int N, double t, double* out);
+
+/* The translational part of the 3f condensed Hessian, which depends on
+ * (N, t, m) only: out[3][N(N+1)/2], for the axes x, y, z the lower triangle
+ * (row i at i(i+1)/2) of H[(i, a), (j, a)] through (p_a, v_a).  Host only. */
+int hmpc_hess_table(int N, double t, double m, double* out);
+
 int hmpc_destroy(hmpc_ctx* ctx);
 
 /* One QP per instance on the given linearisation x_lin (device pointers).

@@ -3,6 +3,9 @@
 Build:  OUT=libhmpc_stamps.so BDIR=build_stamps HORIZONS=10 \
         hopper-mpc-inertial_amd/build.sh -DHMPC_STAMPS
 Run:    HMPC_LIB=hopper-mpc-inertial_amd/libhmpc_stamps.so python tools/phase_stamps.py
+A build with -DHMPC_STAMPS -DHMPC_STAMPS_P23 (it marks its stamps, so the
+script knows) splits phases 2 and 3 instead of the active set: the cost-to-go recursion, f = S b and the
+adjoint's propagation (profiles/r07_phase23_split.json).
 The stamped kernel writes s_memtime values over each instance's x* row.
 PREC=f32 / f32_refined (REFINE=k) stamp the fp32 builds; in the refined
 build phase 'outputs' is the refinement (fp64 set-up, k corrections, final
@@ -53,6 +56,13 @@ def main():
     it = out['iters'].float().cpu().numpy()
     ref_cyc = out['x'].view(torch.int64).reshape(B, -1)[:, 15].cpu().numpy()
     stamped = (st[:, 0] > 0) & (dur >= 0).all(axis=1) & (tot < 10**8)
+    # a build with -DHMPC_STAMPS_P23 marks slot 15 of every instance it stamps
+    p23 = bool(stamped.any()) and bool((ref_cyc[stamped] == 0x503233).all())
+    if p23 and prec == 'f32_refined':
+        # slot 15 is the refinement's timer in the plain stamped build and the
+        # marker in this one: the split is not reported for this precision
+        sys.exit('a -DHMPC_STAMPS_P23 build does not time the refinement: stamp f32_refined '
+                 'with the plain -DHMPC_STAMPS build')
 
     def summary(m):
         m = m & stamped
@@ -64,6 +74,16 @@ def main():
         res['total_max'] = float(tot[m].max())
         res['iters_mean'] = float(it[m].mean())
         res['instances'] = int(m.sum())
+        if p23:
+            # a build with -DHMPC_STAMPS_P23: slots 9..11 split phases 2 and 3
+            # (each timed part includes its own two s_memtime reads)
+            ctg, sb, adv = (float(acc[m, i].mean()) for i in range(3))
+            res['p2b_ctg_recursion'] = ctg
+            res['p2a_free_response_gradient'] = res['uniform_sweeps'] - ctg
+            res['p3a_s_times_b'] = sb
+            res['p3a_adjoint_propagation'] = adv
+            res['p3b_bd_dots_and_row'] = res['hessian_rows'] - sb - adv
+            return res
         # accumulated active-set sub-phases (slots 9..14 of the stamped build)
         for i, n in enumerate(['gi_scan', 'gi_fwd_sweep', 'gi_gram_schmidt', 'gi_bwd_sweep',
                                'gi_dual_step', 'gi_add_drop']):
