@@ -11,6 +11,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -550,6 +551,71 @@ int check_solve_args(hmpc_ctx* c, int64_t B, const void* x_in, const void* x_lin
   return HMPC_OK;
 }
 
+// the PlantArgs part of the three plant entry points: the constants and the U / pf views
+void fill_plant(hmpc::PlantArgs& a, const hmpc_ctx* c, int64_t B, int n_steps, double dt, const double* J,
+                const double* U, int64_t U_bstride, const double* pf, int64_t pf_bstride, int64_t pf_sstride) {
+  a.B = B; a.n_steps = n_steps; a.dt = dt; a.m = c->m; a.g = c->g;
+  memcpy(a.J, J, sizeof(a.J));
+  memcpy(a.Jinv, c->Jinv, sizeof(a.Jinv));
+  memcpy(a.rh, c->rh, sizeof(a.rh));
+  a.X = nullptr; a.X_hist = nullptr; a.x_out = nullptr;
+  a.U = U; a.U_bs = U_bstride;
+  a.pf = pf; a.pf_bs = pf_bstride; a.pf_ss = pf_sstride;
+}
+
+static_assert(hmpc::kKktNmax == 64 && hmpc::kSensNmax == 64 && hmpc::kVjpNmax == 64, "the message below says 64");
+
+// The checks hmpc_kkt_batch, hmpc_sens_batch, hmpc_vjp_batch and hmpc_vjp_lin_batch
+// share, in the order all four fire them: the context, the variant and N, B and
+// act_tol; the entry point's own argument checks (own(): its message, or nullptr);
+// then B == 0 (HMPC_OK with *run left false), the grid limit and the required
+// pointers (the primal point and its problem data, and the output a call cannot
+// do without: null_msg says which).
+template <class Own>
+int check_point_args(hmpc_ctx* c, const char* name, int64_t B, double act_tol, Own own,
+                     std::initializer_list<const void*> required, const char* null_msg, bool* run) {
+  *run = false;
+  if (!c) return HMPC_ERR_ARG;
+  if (c->variant == HMPC_VARIANT_CAS || c->N > hmpc::kKktNmax) {
+    c->err = std::string(name) + " serves the 3f and 2f variants up to N = 64";
+    return HMPC_ERR_UNSUPPORTED;
+  }
+  if (B < 0 || !(act_tol >= 0.0)) { c->err = "B < 0 or act_tol < 0"; return HMPC_ERR_ARG; }
+  if (const char* msg = own()) { c->err = msg; return HMPC_ERR_ARG; }
+  if (B == 0) return HMPC_OK;
+  if (B > 0x7fffffffLL) { c->err = "B exceeds the grid limit"; return HMPC_ERR_ARG; }
+  for (const void* p : required)
+    if (!p) { c->err = null_msg; return HMPC_ERR_ARG; }
+  *run = true;
+  return HMPC_OK;
+}
+
+bool misaligned(hmpc_ctx* c, std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs)
+    if ((uintptr_t)p % sizeof(double)) { c->err = "misaligned pointer"; return true; }
+  return false;
+}
+
+// the model constants of any of KktArgs, SensArgs, VjpArgs, VjpLinArgs
+template <class Args>
+void fill_model(Args& a, const hmpc_ctx* c, int64_t B, double act_tol) {
+  a.B = B; a.N = c->N;
+  a.dt = c->t; a.m = c->m; a.mu_default = c->mu; a.act_tol = act_tol;
+  memcpy(a.Jinv, c->Jinv, sizeof(a.Jinv));
+  memcpy(a.rh, c->rh, sizeof(a.rh));
+}
+
+// the part of VjpArgs both adjoint entry points fill
+void fill_vjp(hmpc::VjpArgs& a, const hmpc_ctx* c, int64_t B, const double* x_lin, const double* x_ref,
+              const double* pf, const double* C, const double* mu, const double* u, const double* x, double act_tol,
+              const double* g_u, const double* g_x, double* grad_x_in, double* grad_x_ref, double* grad_pf,
+              int32_t* flags) {
+  a.x_lin = x_lin; a.x_ref = x_ref; a.pf = pf; a.C = C; a.mu = mu; a.u = u; a.x = x;
+  a.g_u = g_u; a.g_x = g_x;
+  a.grad_x_in = grad_x_in; a.grad_x_ref = grad_x_ref; a.grad_pf = grad_pf; a.flags = flags;
+  fill_model(a, c, B, act_tol);
+}
+
 }  // namespace
 
 extern "C" {
@@ -968,13 +1034,8 @@ int hmpc_plant_batch(hmpc_ctx* c, int64_t B, int n_steps, double dt, const doubl
   if (U_bstride < 0 || pf_bstride < 0 || pf_sstride < 0) { c->err = "negative stride"; return HMPC_ERR_ARG; }
   HMPC_HIP(c, hipSetDevice(c->device));
   hmpc::PlantArgs a;
-  a.B = B; a.n_steps = n_steps; a.dt = dt; a.m = c->m; a.g = c->g;
-  memcpy(a.J, J, sizeof(a.J));
-  memcpy(a.Jinv, c->Jinv, sizeof(a.Jinv));
-  memcpy(a.rh, c->rh, sizeof(a.rh));
-  a.X = X; a.U = U; a.U_bs = U_bstride;
-  a.pf = pf; a.pf_bs = pf_bstride; a.pf_ss = pf_sstride;
-  a.X_hist = X_hist; a.x_out = x_out;
+  fill_plant(a, c, B, n_steps, dt, J, U, U_bstride, pf, pf_bstride, pf_sstride);
+  a.X = X; a.X_hist = X_hist; a.x_out = x_out;
   hmpc::launch_plant(a, (hipStream_t)stream);
   HMPC_HIP(c, hipGetLastError());
   return HMPC_OK;
@@ -999,13 +1060,7 @@ int hmpc_plant_vjp_batch(hmpc_ctx* c, int64_t B, int n_steps, double dt, const d
   if (n_steps >= 2 && !X_hist) { c->err = "X_hist is required for n_steps >= 2"; return HMPC_ERR_ARG; }
   HMPC_HIP(c, hipSetDevice(c->device));
   hmpc::PlantVjpArgs a;
-  a.B = B; a.n_steps = n_steps; a.dt = dt; a.m = c->m; a.g = c->g;
-  memcpy(a.J, J, sizeof(a.J));
-  memcpy(a.Jinv, c->Jinv, sizeof(a.Jinv));
-  memcpy(a.rh, c->rh, sizeof(a.rh));
-  a.X = nullptr; a.X_hist = nullptr; a.x_out = nullptr;
-  a.U = U; a.U_bs = U_bstride;
-  a.pf = pf; a.pf_bs = pf_bstride; a.pf_ss = pf_sstride;
+  fill_plant(a, c, B, n_steps, dt, J, U, U_bstride, pf, pf_bstride, pf_sstride);
   a.X0 = X0; a.Xh = X_hist;
   a.g_X = g_X; a.g_x_out = g_x_out; a.g_X_hist = g_X_hist;
   a.grad_X0 = grad_X0; a.grad_U = grad_U; a.grad_pf = grad_pf;
@@ -1033,13 +1088,8 @@ int hmpc_plant_fb_batch(hmpc_ctx* c, int64_t B, int n_steps, int stage_steps, do
   if (!J || !X || !U || !K || !x_nom || !pf) { c->err = "null pointer"; return HMPC_ERR_ARG; }
   HMPC_HIP(c, hipSetDevice(c->device));
   hmpc::PlantFbArgs a;
-  a.B = B; a.n_steps = n_steps; a.dt = dt; a.m = c->m; a.g = c->g;
-  memcpy(a.J, J, sizeof(a.J));
-  memcpy(a.Jinv, c->Jinv, sizeof(a.Jinv));
-  memcpy(a.rh, c->rh, sizeof(a.rh));
-  a.X = X; a.U = U; a.U_bs = U_bstride;
-  a.pf = pf; a.pf_bs = pf_bstride; a.pf_ss = pf_sstride;
-  a.X_hist = X_hist; a.x_out = x_out;
+  fill_plant(a, c, B, n_steps, dt, J, U, U_bstride, pf, pf_bstride, pf_sstride);
+  a.X = X; a.X_hist = X_hist; a.x_out = x_out;
   a.stage_steps = stage_steps; a.flags = flags;
   a.fy_zero = c->variant == HMPC_VARIANT_2F ? 1 : 0;
   a.K = K; a.K_bs = K_bstride;
@@ -1066,28 +1116,17 @@ int hmpc_convert_batch(hmpc_ctx* c, int64_t B, const double* X, double* x, void*
 int hmpc_kkt_batch(hmpc_ctx* c, int64_t B, const double* x_in, const double* x_lin, const double* x_ref,
                    const double* pf, const double* C, const double* mu, const double* u, const double* x,
                    double act_tol, double* nu, double* lam, double* cert, int32_t* flags, void* stream) {
-  if (!c) return HMPC_ERR_ARG;
-  if (c->variant == HMPC_VARIANT_CAS || c->N > hmpc::kKktNmax) {
-    c->err = "hmpc_kkt_batch serves the 3f and 2f variants up to N = 64";
-    return HMPC_ERR_UNSUPPORTED;
-  }
-  if (B < 0 || !(act_tol >= 0.0)) { c->err = "B < 0 or act_tol < 0"; return HMPC_ERR_ARG; }
-  if (B == 0) return HMPC_OK;
-  if (B > 0x7fffffffLL) { c->err = "B exceeds the grid limit"; return HMPC_ERR_ARG; }
-  if (!x_in || !x_lin || !x_ref || !pf || !C || !u || !x || !cert) {
-    c->err = "null input/output pointer";
-    return HMPC_ERR_ARG;
-  }
+  bool run;
+  int rc = check_point_args(c, "hmpc_kkt_batch", B, act_tol, [] { return (const char*)nullptr; },
+                            {x_in, x_lin, x_ref, pf, C, u, x, cert}, "null input/output pointer", &run);
+  if (!run) return rc;
   HMPC_HIP(c, hipSetDevice(c->device));
   hmpc::KktArgs a;
   a.x_in = x_in; a.x_lin = x_lin; a.x_ref = x_ref; a.pf = pf; a.C = C; a.mu = mu; a.u = u; a.x = x;
   a.nu = nu; a.lam = lam; a.cert = cert; a.flags = flags;
-  a.B = B; a.N = c->N;
-  a.dt = c->t; a.m = c->m; a.g = c->g; a.mu_default = c->mu; a.act_tol = act_tol;
-  memcpy(a.Jinv, c->Jinv, sizeof(a.Jinv));
-  memcpy(a.rh, c->rh, sizeof(a.rh));
+  fill_model(a, c, B, act_tol);
+  a.g = c->g;
   a.uref_aliased = c->uref_mode == HMPC_UREF_ALIASED ? 1 : 0;
-  int rc;
   if ((rc = order_stream(c, (hipStream_t)stream)) != HMPC_OK) return rc;
   hmpc::launch_kkt(c->variant, a, (hipStream_t)stream);
   HMPC_HIP(c, hipGetLastError());
@@ -1097,30 +1136,20 @@ int hmpc_kkt_batch(hmpc_ctx* c, int64_t B, const double* x_in, const double* x_l
 int hmpc_sens_batch(hmpc_ctx* c, int64_t B, const double* x_in, const double* x_lin, const double* x_ref,
                     const double* pf, const double* C, const double* mu, const double* u, const double* x,
                     double act_tol, int n_stages, double* S, int32_t* flags, void* stream) {
-  if (!c) return HMPC_ERR_ARG;
-  if (c->variant == HMPC_VARIANT_CAS || c->N > hmpc::kSensNmax) {
-    c->err = "hmpc_sens_batch serves the 3f and 2f variants up to N = 64";
-    return HMPC_ERR_UNSUPPORTED;
-  }
-  if (B < 0 || !(act_tol >= 0.0)) { c->err = "B < 0 or act_tol < 0"; return HMPC_ERR_ARG; }
-  if (n_stages < 1 || n_stages > c->N) { c->err = "n_stages outside 1..N"; return HMPC_ERR_ARG; }
-  if (B == 0) return HMPC_OK;
-  if (B > 0x7fffffffLL) { c->err = "B exceeds the grid limit"; return HMPC_ERR_ARG; }
   // x_in and x_ref do not enter the Jacobian (they move the optimum, not its
   // slope); they are required so that the call reads like hmpc_solve_batch
-  if (!x_in || !x_lin || !x_ref || !pf || !C || !u || !x || !S) {
-    c->err = "null input/output pointer";
-    return HMPC_ERR_ARG;
-  }
+  bool run;
+  int rc = check_point_args(
+      c, "hmpc_sens_batch", B, act_tol,
+      [&] { return (n_stages < 1 || n_stages > c->N) ? "n_stages outside 1..N" : nullptr; },
+      {x_in, x_lin, x_ref, pf, C, u, x, S}, "null input/output pointer", &run);
+  if (!run) return rc;
   HMPC_HIP(c, hipSetDevice(c->device));
   hmpc::SensArgs a;
   a.x_lin = x_lin; a.pf = pf; a.C = C; a.mu = mu; a.u = u; a.x = x;
   a.S = S; a.flags = flags;
-  a.B = B; a.N = c->N; a.n_stages = n_stages;
-  a.dt = c->t; a.m = c->m; a.mu_default = c->mu; a.act_tol = act_tol;
-  memcpy(a.Jinv, c->Jinv, sizeof(a.Jinv));
-  memcpy(a.rh, c->rh, sizeof(a.rh));
-  int rc;
+  a.n_stages = n_stages;
+  fill_model(a, c, B, act_tol);
   if ((rc = order_stream(c, (hipStream_t)stream)) != HMPC_OK) return rc;
   hmpc::launch_sens(c->variant, a, (hipStream_t)stream);
   HMPC_HIP(c, hipGetLastError());
@@ -1131,31 +1160,22 @@ int hmpc_vjp_batch(hmpc_ctx* c, int64_t B, const double* x_in, const double* x_l
                    const double* pf, const double* C, const double* mu, const double* u, const double* x,
                    double act_tol, const double* g_u, const double* g_x, double* grad_x_in, double* grad_x_ref,
                    double* grad_pf, int32_t* flags, void* stream) {
-  if (!c) return HMPC_ERR_ARG;
-  if (c->variant == HMPC_VARIANT_CAS || c->N > hmpc::kVjpNmax) {
-    c->err = "hmpc_vjp_batch serves the 3f and 2f variants up to N = 64";
-    return HMPC_ERR_UNSUPPORTED;
-  }
-  if (B < 0 || !(act_tol >= 0.0)) { c->err = "B < 0 or act_tol < 0"; return HMPC_ERR_ARG; }
-  if (!g_u && !g_x) { c->err = "both cotangents are null"; return HMPC_ERR_ARG; }
-  if (!grad_x_in && !grad_x_ref && !grad_pf) { c->err = "every gradient output is null"; return HMPC_ERR_ARG; }
-  if (B == 0) return HMPC_OK;
-  if (B > 0x7fffffffLL) { c->err = "B exceeds the grid limit"; return HMPC_ERR_ARG; }
   // x_in does not enter (x[:,0] is the same point); required so that the call reads like hmpc_sens_batch
-  if (!x_in || !x_lin || !x_ref || !pf || !C || !u || !x) { c->err = "null input pointer"; return HMPC_ERR_ARG; }
-  const void* ptrs[] = {x_in, x_lin, x_ref, pf, C, mu, u, x, g_u, g_x, grad_x_in, grad_x_ref, grad_pf};
-  for (const void* p : ptrs)
-    if ((uintptr_t)p % sizeof(double)) { c->err = "misaligned pointer"; return HMPC_ERR_ARG; }
+  bool run;
+  int rc = check_point_args(
+      c, "hmpc_vjp_batch", B, act_tol,
+      [&]() -> const char* {
+        if (!g_u && !g_x) return "both cotangents are null";
+        if (!grad_x_in && !grad_x_ref && !grad_pf) return "every gradient output is null";
+        return nullptr;
+      },
+      {x_in, x_lin, x_ref, pf, C, u, x}, "null input pointer", &run);
+  if (!run) return rc;
+  if (misaligned(c, {x_in, x_lin, x_ref, pf, C, mu, u, x, g_u, g_x, grad_x_in, grad_x_ref, grad_pf}))
+    return HMPC_ERR_ARG;
   HMPC_HIP(c, hipSetDevice(c->device));
   hmpc::VjpArgs a;
-  a.x_lin = x_lin; a.x_ref = x_ref; a.pf = pf; a.C = C; a.mu = mu; a.u = u; a.x = x;
-  a.g_u = g_u; a.g_x = g_x;
-  a.grad_x_in = grad_x_in; a.grad_x_ref = grad_x_ref; a.grad_pf = grad_pf; a.flags = flags;
-  a.B = B; a.N = c->N;
-  a.dt = c->t; a.m = c->m; a.mu_default = c->mu; a.act_tol = act_tol;
-  memcpy(a.Jinv, c->Jinv, sizeof(a.Jinv));
-  memcpy(a.rh, c->rh, sizeof(a.rh));
-  int rc;
+  fill_vjp(a, c, B, x_lin, x_ref, pf, C, mu, u, x, act_tol, g_u, g_x, grad_x_in, grad_x_ref, grad_pf, flags);
   if ((rc = order_stream(c, (hipStream_t)stream)) != HMPC_OK) return rc;
   hmpc::launch_vjp(c->variant, a, (hipStream_t)stream);
   HMPC_HIP(c, hipGetLastError());
@@ -1167,36 +1187,24 @@ int hmpc_vjp_lin_batch(hmpc_ctx* c, int64_t B, const double* x_in, const double*
                        double act_tol, const double* nu, const double* lam, const double* g_u, const double* g_x,
                        double* grad_x_in, double* grad_x_ref, double* grad_pf, double* grad_x_lin,
                        double* grad_mu, int32_t* flags, void* stream) {
-  if (!c) return HMPC_ERR_ARG;
-  if (c->variant == HMPC_VARIANT_CAS || c->N > hmpc::kVjpNmax) {
-    c->err = "hmpc_vjp_lin_batch serves the 3f and 2f variants up to N = 64";
-    return HMPC_ERR_UNSUPPORTED;
-  }
-  if (B < 0 || !(act_tol >= 0.0)) { c->err = "B < 0 or act_tol < 0"; return HMPC_ERR_ARG; }
-  if (!g_u && !g_x) { c->err = "both cotangents are null"; return HMPC_ERR_ARG; }
-  if (!grad_x_in && !grad_x_ref && !grad_pf && !grad_x_lin && !grad_mu) {
-    c->err = "every gradient output is null";
+  bool run;
+  int rc = check_point_args(
+      c, "hmpc_vjp_lin_batch", B, act_tol,
+      [&]() -> const char* {
+        if (!g_u && !g_x) return "both cotangents are null";
+        if (!grad_x_in && !grad_x_ref && !grad_pf && !grad_x_lin && !grad_mu) return "every gradient output is null";
+        if (!nu || !lam) return "the multipliers nu and lam are required (hmpc_kkt_batch)";
+        return nullptr;
+      },
+      {x_in, x_lin, x_ref, pf, C, u, x}, "null input pointer", &run);
+  if (!run) return rc;
+  if (misaligned(c, {x_in, x_lin, x_ref, pf, C, mu, u, x, nu, lam, g_u, g_x, grad_x_in, grad_x_ref, grad_pf,
+                     grad_x_lin, grad_mu}))
     return HMPC_ERR_ARG;
-  }
-  if (!nu || !lam) { c->err = "the multipliers nu and lam are required (hmpc_kkt_batch)"; return HMPC_ERR_ARG; }
-  if (B == 0) return HMPC_OK;
-  if (B > 0x7fffffffLL) { c->err = "B exceeds the grid limit"; return HMPC_ERR_ARG; }
-  if (!x_in || !x_lin || !x_ref || !pf || !C || !u || !x) { c->err = "null input pointer"; return HMPC_ERR_ARG; }
-  const void* ptrs[] = {x_in, x_lin, x_ref, pf, C, mu, u, x, nu, lam, g_u, g_x,
-                        grad_x_in, grad_x_ref, grad_pf, grad_x_lin, grad_mu};
-  for (const void* p : ptrs)
-    if ((uintptr_t)p % sizeof(double)) { c->err = "misaligned pointer"; return HMPC_ERR_ARG; }
   HMPC_HIP(c, hipSetDevice(c->device));
   hmpc::VjpLinArgs a;
-  a.x_lin = x_lin; a.x_ref = x_ref; a.pf = pf; a.C = C; a.mu = mu; a.u = u; a.x = x;
-  a.g_u = g_u; a.g_x = g_x;
-  a.grad_x_in = grad_x_in; a.grad_x_ref = grad_x_ref; a.grad_pf = grad_pf; a.flags = flags;
+  fill_vjp(a, c, B, x_lin, x_ref, pf, C, mu, u, x, act_tol, g_u, g_x, grad_x_in, grad_x_ref, grad_pf, flags);
   a.lam = lam; a.grad_x_lin = grad_x_lin; a.grad_mu = grad_mu;   // nu: see DESIGN.md 4.10 (no term reads it)
-  a.B = B; a.N = c->N;
-  a.dt = c->t; a.m = c->m; a.mu_default = c->mu; a.act_tol = act_tol;
-  memcpy(a.Jinv, c->Jinv, sizeof(a.Jinv));
-  memcpy(a.rh, c->rh, sizeof(a.rh));
-  int rc;
   if ((rc = order_stream(c, (hipStream_t)stream)) != HMPC_OK) return rc;
   hmpc::launch_vjp_lin(c->variant, a, (hipStream_t)stream);
   HMPC_HIP(c, hipGetLastError());

@@ -24,30 +24,25 @@
 // No MFMA: the blocks are 12 x 6 and smaller.
 #include <hip/hip_runtime.h>
 
-#include <utility>
-
 #include "hmpc_internal.h"
 #include "hmpc_model.h"
+#include "hmpc_sens_common.h"
 
 namespace hmpc {
 
 namespace {
 
-constexpr int kRec = 48;   // doubles per stage record
-// offsets inside a stage record
-constexpr int R_CS = 0;    // cos, sin of the linearisation yaw
-constexpr int R_BW = 2;    // rows 9..11 of Bd_k, [3][6]
-constexpr int R_CX = 20;   // 2 kappa_k Q (x_{k+1} - r_k)
-constexpr int R_DU = 32;   // 2 lambda_k R (u_k - ubar_k)
-constexpr int R_PI = 38;   // force projector, symmetric: xx xy xz yy yz zz
-constexpr int R_TM = 44;   // torque mask (1: the component must vanish)
-constexpr double kPivotFloor = 1e-11;   // relative to the row's own diagonal
+// the stage record (longer than the one sens / vjp share: it carries the cost gradients)
+constexpr int kKktRec = 48;   // doubles per stage record
+constexpr int KR_CS = 0;    // cos, sin of the linearisation yaw
+constexpr int KR_BW = 2;    // rows 9..11 of Bd_k, [3][6]
+constexpr int KR_CX = 20;   // 2 kappa_k Q (x_{k+1} - r_k)
+constexpr int KR_DU = 32;   // 2 lambda_k R (u_k - ubar_k)
+constexpr int KR_PI = 38;   // force projector, symmetric: xx xy xz yy yz zz
+constexpr int KR_TM = 44;   // torque mask (1: the component must vanish), contiguous with KR_PI
 
 // stage classes
 constexpr int CL_SWING = 0, CL_APEX = 1, CL_REG = 2;
-// active-mask bits
-constexpr int A_FXP = 1, A_FXM = 2, A_FYP = 4, A_FYM = 8, A_FZU = 16;
-constexpr int A_TUP = 32, A_TLO = 256;   // << c for torque c
 
 __device__ __forceinline__ double wave_max(double x) {
   x = fmax(x, dpp<kDppXor1>(x));
@@ -57,129 +52,26 @@ __device__ __forceinline__ double wave_max(double x) {
   return fmax(fmax(rdlane(x, 0), rdlane(x, 16)), fmax(rdlane(x, 32), rdlane(x, 48)));
 }
 
-// Orthonormal basis (modified Gram-Schmidt) of the active force rows of a
-// regular stance stage: at most one of +-fx - mu fz, one of +-fy - mu fz (2f:
-// the fixed fy) and fz <= f_max; always independent.  rr holds the
-// reciprocal norms on its diagonal (0 for an absent column).
-struct StageQr {
-  double q[3][3];
-  double r01, r02, r12;
-  double ri[3];
-};
-template <int VAR>
-__device__ __forceinline__ void stage_qr(int mask, double mu, StageQr& s) {
-  const bool px = (mask & (A_FXP | A_FXM)) != 0;
-  const bool py = VAR == 2 ? true : (mask & (A_FYP | A_FYM)) != 0;
-  const bool pz = (mask & A_FZU) != 0;
-  const double sx = (mask & A_FXP) ? 1.0 : -1.0;
-  const double sy = (mask & A_FYP) ? 1.0 : -1.0;
-  double a[3][3] = {{px ? sx : 0.0, 0.0, px ? -mu : 0.0},
-                    {0.0, py ? (VAR == 2 ? 1.0 : sy) : 0.0, (py && VAR != 2) ? -mu : 0.0},
-                    {0.0, 0.0, pz ? 1.0 : 0.0}};
-  const bool pres[3] = {px, py, pz};
-  double r[3][3] = {};
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < i; ++j) {
-      r[j][i] = s.q[j][0] * a[i][0] + s.q[j][1] * a[i][1] + s.q[j][2] * a[i][2];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) a[i][c] = fma(-r[j][i], s.q[j][c], a[i][c]);
-    }
-    const double n2 = a[i][0] * a[i][0] + a[i][1] * a[i][1] + a[i][2] * a[i][2];
-    s.ri[i] = (pres[i] && n2 > 0.0) ? 1.0 / sqrt(n2) : 0.0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) s.q[i][c] = a[i][c] * s.ri[i];
-  }
-  s.r01 = r[0][1]; s.r02 = r[0][2]; s.r12 = r[1][2];
-}
-
-// m = Bd_k' P (rows 6..8: bv(); rows 9..11: the record's bw)
-template <int VAR>
-__device__ __forceinline__ void bdt_times(const double (&P)[12], const double* rec, double dtm,
-                                          double (&m)[6]) {
-  const double cp = rec[R_CS], sp = rec[R_CS + 1];
-#pragma unroll
-  for (int c = 0; c < 6; ++c) {
-    double acc = 0.0;
-    if (c < 3) {
-      if constexpr (VAR == 3) {
-        acc = dtm * P[6 + c];
-      } else {
-#pragma unroll
-        for (int r = 0; r < 3; ++r) acc = fma(bv<VAR>(r, c, dtm, cp, sp), P[6 + r], acc);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 3; ++r) acc = fma(rec[R_BW + 6 * r + c], P[9 + r], acc);
-    m[c] = acc;
-  }
-}
-
 // One backward step shared by pass 1 and pass 2: m = Bd_k' P + base du_k, then
 // (k > 0) P <- Ad_k' P + base cx_{k-1} + [this lane's z row is stage k] e_2.
 template <int VAR>
 __device__ __forceinline__ void back_step(int k, const double* recs, double dt, double dtm, double base,
                                           int zstage, double (&P)[12], double (&m)[6]) {
-  const double* rec = recs + kRec * k;
-  bdt_times<VAR>(P, rec, dtm, m);
+  const double* rec = recs + kKktRec * k;
+  bdt_times<VAR>(P, rec[KR_CS], rec[KR_CS + 1], rec + KR_BW, dtm, m);
 #pragma unroll
-  for (int c = 0; c < 6; ++c) m[c] = fma(base, rec[R_DU + c], m[c]);
+  for (int c = 0; c < 6; ++c) m[c] = fma(base, rec[KR_DU + c], m[c]);
   if (k > 0) {
-    adt_times(P, dt, rec[R_CS], rec[R_CS + 1]);
-    const double* prev = rec - kRec;
+    adt_times(P, dt, rec[KR_CS], rec[KR_CS + 1]);
+    const double* prev = rec - kKktRec;
 #pragma unroll
-    for (int r = 0; r < 12; ++r) P[r] = fma(base, prev[R_CX + r], P[r]);
+    for (int r = 0; r < 12; ++r) P[r] = fma(base, prev[KR_CX + r], P[r]);
     P[2] += (zstage == k) ? 1.0 : 0.0;
   }
 }
 
-// Step C of the elimination of the q x q normal equations, row per lane: the
-// pivot row comes from lane C by readlane (every register index is a
-// template constant, so the Gram row stays in registers), columns in blocks
-// of eight up to nq.  Column 0 is the right-hand side.
-template <int C>
-__device__ __forceinline__ void eliminate_step(double (&G)[64], double D0, int nq, int lane, int& singular,
-                                               double& rinv_own) {
-  if (C > nq) return;
-  const double piv = rdlane(G[C], C);
-  const double d0 = rdlane(D0, C);
-  const bool ok = piv > kPivotFloor * d0 && piv > 0.0;
-  const double rinv = ok ? 1.0 / piv : 0.0;
-  singular |= ok ? 0 : 1;
-  rinv_own = lane == C ? rinv : rinv_own;
-  const double f = lane > C ? G[C] * rinv : 0.0;
-  G[0] = fma(-f, rdlane(G[0], C), G[0]);
-#pragma unroll
-  for (int jb = 0; jb < 64; jb += 8) {
-    if (jb + 7 > C && jb <= nq) {
-#pragma unroll
-      for (int j = jb; j < jb + 8; ++j)
-        if (j > C) G[j] = fma(-f, rdlane(G[j], C), G[j]);
-    }
-  }
-}
-template <int... Cs>
-__device__ __forceinline__ void eliminate(std::integer_sequence<int, Cs...>, double (&G)[64], double D0, int nq,
-                                          int lane, int& singular, double& rinv_own) {
-  (eliminate_step<Cs + 1>(G, D0, nq, lane, singular, rinv_own), ...);
-}
-// nu_C = rhs_C / pivot_C from lane C, C = 63 .. 1; the rows above take it out
-template <int C>
-__device__ __forceinline__ void back_step_nu(double (&G)[64], int nq, int lane, double rinv_own, double& nu_own) {
-  if (C > nq) return;
-  const double nc = rdlane(G[0] * rinv_own, C);
-  nu_own = lane == C ? nc : nu_own;
-  G[0] = (lane < C) ? fma(-G[C], nc, G[0]) : G[0];
-}
-template <int... Cs>
-__device__ __forceinline__ void back_substitute(std::integer_sequence<int, Cs...>, double (&G)[64], int nq,
-                                                int lane, double rinv_own, double& nu_own) {
-  (back_step_nu<63 - Cs>(G, nq, lane, rinv_own, nu_own), ...);
-}
-
 struct KktShared {
-  double rec[65 * kRec];   // one spare record / row / slot for the idle lanes
+  double rec[65 * kKktRec];   // one spare record / row / slot for the idle lanes
   double tile[64 * 6];
   double nu[65];
   double lam[65 * 11];
@@ -217,7 +109,7 @@ __global__ void __launch_bounds__(64) kkt_kernel(KktArgs a) {
       const double pfk[3] = {pfp[0], pfp[1], pfp[2]};
       stage_dynamics_vals<VAR, double>(0, xl[5], p, pfk, a.Jinv, a.rh, dt, cs, bw);
     }
-    double* rec = sh.rec + kRec * (st ? lane : 64);   // idle lanes write a spare record
+    double* rec = sh.rec + kKktRec * (st ? lane : 64);   // idle lanes write a spare record
     double peq = 0.0, pin = 0.0, qmax = 0.0;
     // u_ref of this stage's cost (aliased: the last stage's)
     const bool uref_on = a.uref_aliased ? (a.C[b * N + N - 1] != 0.0) : stance;
@@ -255,12 +147,13 @@ __global__ void __launch_bounds__(64) kkt_kernel(KktArgs a) {
 #pragma unroll
       for (int r = 0; r < 12; ++r) peq = fmax(peq, lane == 0 ? fabs(x0[r] - a.x_in[b * 12 + r]) : 0.0);
     }
+    // the active set by the shared rule; the slacks stay for the certificate
+    const StageClass sc = classify_stage<VAR>(u, x0[2], stance, mu, tol);
     // z row of this stage (nu_0 = 0: that row sits on the fixed x_0)
-    const double zslack = x0[2] - kZmin;
+    const double zslack = sc.zslack;
     pin = fmax(pin, -zslack);
-    const bool zact = st && lane >= 1 && zslack <= tol * (1.0 + kZmin);
+    const bool zact = st && lane >= 1 && sc.zact;
     // torques
-    int mask = 0;
     double tsl[3];   // slack of the active (or nearer) torque bound
     double tm[3];
 #pragma unroll
@@ -268,68 +161,42 @@ __global__ void __launch_bounds__(64) kkt_kernel(KktArgs a) {
       const double lim = tau_lim(3 + c);
       const double sup = lim - u[3 + c], slo = u[3 + c] + lim;
       pin = fmax(pin, fmax(-sup, -slo));
-      const bool up = sup <= tol * (1.0 + lim);
-      const bool lo = !up && slo <= tol * (1.0 + lim);
-      mask |= up ? (A_TUP << c) : 0;
-      mask |= lo ? (A_TLO << c) : 0;
-      tsl[c] = up ? sup : slo;
-      tm[c] = (up || lo) ? 0.0 : 1.0;
+      tsl[c] = (sc.tmask & (A_TUP << c)) ? sup : slo;
+      tm[c] = torque_free(sc, c);
     }
-    // forces: stage class, active rows and projector, branch-free (selects)
+    // forces, branch-free (selects)
     if (VAR == 2) peq = fmax(peq, fabs(u[1]));
     peq = fmax(peq, stance ? 0.0 : fmax(fabs(u[0]), fmax(fabs(u[1]), fabs(u[2]))));
     const double szl = u[2], szu = kFzMax - u[2];
-    const bool apex = stance && szl <= tol;
-    const bool reg = stance && !apex;
+    const bool apex = sc.apex, reg = sc.reg;
     const int cls = !stance ? CL_SWING : (apex ? CL_APEX : CL_REG);
     double fsl[5];   // slacks of slots 3..6 and of the fz bound in play (0 on swing stages)
-    fsl[0] = stance ? mu * u[2] - u[0] : 0.0;
-    fsl[1] = stance ? mu * u[2] + u[0] : 0.0;
-    fsl[2] = (stance && VAR == 3) ? mu * u[2] - u[1] : 0.0;
-    fsl[3] = (stance && VAR == 3) ? mu * u[2] + u[1] : 0.0;
+    fsl[0] = stance ? sc.fs[0] : 0.0;
+    fsl[1] = stance ? sc.fs[1] : 0.0;
+    fsl[2] = (stance && VAR == 3) ? sc.fs[2] : 0.0;
+    fsl[3] = (stance && VAR == 3) ? sc.fs[3] : 0.0;
     fsl[4] = stance ? (apex ? szl : szu) : 0.0;
     pin = fmax(pin, stance ? fmax(fmax(-fsl[0], -fsl[1]), fmax(-szl, -szu)) : 0.0);
     pin = fmax(pin, fmax(-fsl[2], -fsl[3]));
-    {
-      const bool a3 = fsl[0] <= tol, a4 = fsl[1] <= tol, a5 = fsl[2] <= tol, a6 = fsl[3] <= tol;
-      const bool xp = a3 && (!a4 || fsl[0] <= fsl[1]);
-      const bool yp = a5 && (!a6 || fsl[2] <= fsl[3]);
-      int fm = xp ? A_FXP : (a4 ? A_FXM : 0);
-      if (VAR == 3) fm |= yp ? A_FYP : (a6 ? A_FYM : 0);
-      fm |= (szu <= tol * (1.0 + kFzMax)) ? A_FZU : 0;
-      mask |= reg ? fm : 0;
-    }
+    const int mask = sc.tmask | (reg ? sc.fm : 0);   // the rows that receive a multiplier
     double pi[6];
-    {
-      StageQr s;
-      stage_qr<VAR>(mask, mu, s);
-      pi[0] = 1.0; pi[1] = 0.0; pi[2] = 0.0; pi[3] = 1.0; pi[4] = 0.0; pi[5] = 1.0;
+    force_projector<VAR>(mask, mu, pi);
+    // swing and apex stages: every force component is free
 #pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        pi[0] = fma(-s.q[i][0], s.q[i][0], pi[0]);
-        pi[1] = fma(-s.q[i][0], s.q[i][1], pi[1]);
-        pi[2] = fma(-s.q[i][0], s.q[i][2], pi[2]);
-        pi[3] = fma(-s.q[i][1], s.q[i][1], pi[3]);
-        pi[4] = fma(-s.q[i][1], s.q[i][2], pi[4]);
-        pi[5] = fma(-s.q[i][2], s.q[i][2], pi[5]);
-      }
-      // swing and apex stages: every force component is free
-#pragma unroll
-      for (int i = 0; i < 6; ++i) pi[i] = reg ? pi[i] : 0.0;
-    }
+    for (int i = 0; i < 6; ++i) pi[i] = reg ? pi[i] : 0.0;
     __syncthreads();   // the previous instance's reads of the shared block are done
-    rec[R_CS] = cs[0];
-    rec[R_CS + 1] = cs[1];
+    rec[KR_CS] = cs[0];
+    rec[KR_CS + 1] = cs[1];
 #pragma unroll
-    for (int i = 0; i < 18; ++i) rec[R_BW + i] = bw[i];
+    for (int i = 0; i < 18; ++i) rec[KR_BW + i] = bw[i];
 #pragma unroll
-    for (int r = 0; r < 12; ++r) rec[R_CX + r] = cx[r];
+    for (int r = 0; r < 12; ++r) rec[KR_CX + r] = cx[r];
 #pragma unroll
-    for (int c = 0; c < 6; ++c) rec[R_DU + c] = du[c];
+    for (int c = 0; c < 6; ++c) rec[KR_DU + c] = du[c];
 #pragma unroll
-    for (int i = 0; i < 6; ++i) rec[R_PI + i] = pi[i];
+    for (int i = 0; i < 6; ++i) rec[KR_PI + i] = pi[i];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) rec[R_TM + c] = tm[c];
+    for (int c = 0; c < 3; ++c) rec[KR_TM + c] = tm[c];
     sh.nu[lane] = 0.0;
     peq = wave_max(st ? peq : 0.0);
     pin = wave_max(st ? pin : 0.0);
@@ -350,40 +217,21 @@ __global__ void __launch_bounds__(64) kkt_kernel(KktArgs a) {
     double D0 = 0.0;
     if (nq > 0) {
       {
-        const double* lastrec = sh.rec + kRec * (N - 1);
+        const double* lastrec = sh.rec + kKktRec * (N - 1);
 #pragma unroll
-        for (int r = 0; r < 12; ++r) P[r] = base * lastrec[R_CX + r];
+        for (int r = 0; r < 12; ++r) P[r] = base * lastrec[KR_CX + r];
       }
 #pragma unroll 1
       for (int kk = N - 1; kk >= 0; --kk) {
         back_step<VAR>(kk, sh.rec, dt, dtm, base, zstage, P, m);
-        const double* rk = sh.rec + kRec * kk;
-        double mt[6];
-        mt[0] = rk[R_PI + 0] * m[0] + rk[R_PI + 1] * m[1] + rk[R_PI + 2] * m[2];
-        mt[1] = rk[R_PI + 1] * m[0] + rk[R_PI + 3] * m[1] + rk[R_PI + 4] * m[2];
-        mt[2] = rk[R_PI + 2] * m[0] + rk[R_PI + 4] * m[1] + rk[R_PI + 5] * m[2];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) mt[3 + c] = rk[R_TM + c] * m[3 + c];
+        pi_apply(sh.rec + kKktRec * kk + KR_PI, m);   // the components that must vanish
 #pragma unroll
         for (int c = 0; c < 6; ++c) {
-          sh.tile[6 * lane + c] = mt[c];
-          D0 = fma(mt[c], mt[c], D0);
+          sh.tile[6 * lane + c] = m[c];
+          D0 = fma(m[c], m[c], D0);
         }
         __syncthreads();
-        // own Gram row from broadcast reads of the tile, eight columns a block
-#pragma unroll
-        for (int jb = 0; jb < 64; jb += 8) {
-          if (jb <= nq) {
-#pragma unroll
-            for (int j = jb; j < jb + 8; ++j) {
-              const double* t = sh.tile + 6 * j;
-              double acc = G[j];
-#pragma unroll
-              for (int c = 0; c < 6; ++c) acc = fma(mt[c], t[c], acc);
-              G[j] = acc;
-            }
-          }
-        }
+        gram_row(G, m, sh.tile, nq + 1);   // own Gram row, columns 0..nq
         __syncthreads();
       }
     }
@@ -393,9 +241,9 @@ __global__ void __launch_bounds__(64) kkt_kernel(KktArgs a) {
     // readlane.  A pivot below the floor: the row is dependent given the
     // pinned inputs -- flag it and leave its nu at 0.
     int singular = 0;
-    double rinv_own = 0.0, nu_own = 0.0;
-    eliminate(std::make_integer_sequence<int, 63>(), G, D0, nq, lane, singular, rinv_own);
-    back_substitute(std::make_integer_sequence<int, 63>(), G, nq, lane, rinv_own, nu_own);
+    double rhs[1] = {G[0]};
+    solve_rows<1, 1>(G, rhs, D0, nq, lane, singular);
+    const double nu_own = zstage >= 0 ? rhs[0] : 0.0;
     sh.nu[zstage >= 0 ? zstage : 64] = nu_own;   // slot 64: spare
     __syncthreads();
     const double nuk = sh.nu[lane];   // nu of this lane's stage
@@ -404,9 +252,9 @@ __global__ void __launch_bounds__(64) kkt_kernel(KktArgs a) {
     double g[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     {
       const double coef = lane == 0 ? 1.0 : -nu_own;
-      const double* lastrec = sh.rec + kRec * (N - 1);
+      const double* lastrec = sh.rec + kKktRec * (N - 1);
 #pragma unroll
-      for (int r = 0; r < 12; ++r) P[r] = base * lastrec[R_CX + r];
+      for (int r = 0; r < 12; ++r) P[r] = base * lastrec[KR_CX + r];
 #pragma unroll 1
       for (int kk = N - 1; kk >= 0; --kk) {
         back_step<VAR>(kk, sh.rec, dt, dtm, base, zstage, P, m);

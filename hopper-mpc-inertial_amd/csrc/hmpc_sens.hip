@@ -33,8 +33,6 @@
 // chain that bounds pass 1.
 #include <hip/hip_runtime.h>
 
-#include <utility>
-
 #include "hmpc_internal.h"
 #include "hmpc_model.h"
 #include "hmpc_sens_common.h"
@@ -49,7 +47,7 @@ template <int VAR>
 __device__ __forceinline__ void sweep_step(const double* rec, const double* cf, const double* Kk, double dt,
                                            double dtm, double (&P)[12], double (&y)[6]) {
   double g[6];
-  bdt_times<VAR>(P, rec, dtm, g);
+  bdt_times<VAR>(P, rec[R_CS], rec[R_CS + 1], rec + R_BW, dtm, g);
 #pragma unroll
   for (int c = 0; c < 6; ++c) y[c] = g[c];
   pi_apply(rec + R_PI, y);
@@ -64,58 +62,7 @@ __device__ __forceinline__ void sweep_step(const double* rec, const double* cf, 
   }
 }
 
-// Step C of the elimination of W nu = p_0, row per lane: the pivot row comes
-// from lane C by readlane (every register index is a template constant, so
-// the rows stay in registers), W's columns in blocks of eight up to nq.
-template <int C>
-__device__ __forceinline__ void eliminate_step(double (&G)[64], double (&P)[12], double D0, int nq, int lane,
-                                               int& singular, double& rinv_own) {
-  if (C >= nq) return;
-  const double piv = rdlane(G[C], C);
-  const double d0 = rdlane(D0, C);
-  const bool ok = piv > kPivotFloor * d0 && piv > 0.0;
-  const double rinv = ok ? 1.0 / piv : 0.0;
-  singular |= ok ? 0 : 1;
-  rinv_own = lane == C ? rinv : rinv_own;
-  const double f = lane > C ? G[C] * rinv : 0.0;
-#pragma unroll
-  for (int i = 0; i < 12; ++i) P[i] = fma(-f, rdlane(P[i], C), P[i]);
-#pragma unroll
-  for (int jb = 0; jb < 64; jb += 8) {
-    if (jb + 7 > C && jb < nq) {
-#pragma unroll
-      for (int j = jb; j < jb + 8; ++j)
-        if (j > C) G[j] = fma(-f, rdlane(G[j], C), G[j]);
-    }
-  }
-}
-template <int... Cs>
-__device__ __forceinline__ void eliminate(std::integer_sequence<int, Cs...>, double (&G)[64], double (&P)[12],
-                                          double D0, int nq, int lane, int& singular, double& rinv_own) {
-  (eliminate_step<Cs>(G, P, D0, nq, lane, singular, rinv_own), ...);
-}
-// nu_C = rhs_C / pivot_C stays in lane C (0 for a dropped row); the rows above take it out
-template <int C>
-__device__ __forceinline__ void back_step_nu(const double (&G)[64], double (&P)[12], int nq, int lane,
-                                             double rinv_own) {
-  if (C >= nq) return;
-#pragma unroll
-  for (int i = 0; i < 12; ++i) {
-    const double nc = rdlane(P[i] * rinv_own, C);
-    P[i] = lane == C ? nc : (lane < C ? fma(-G[C], nc, P[i]) : P[i]);
-  }
-}
-template <int... Cs>
-__device__ __forceinline__ void back_substitute(std::integer_sequence<int, Cs...>, const double (&G)[64],
-                                                double (&P)[12], int nq, int lane, double rinv_own) {
-  (back_step_nu<63 - Cs>(G, P, nq, lane, rinv_own), ...);
-}
-
-struct SensShared {
-  double rec[65 * kRec];     // one spare record / row / slot for the idle lanes
-  double K[64 * kKst + 8];
-  double cf[64 * kCst];
-  double tile[64 * 6];       // pass 1: Bd'P | Bd'P Ad, [12][6] each; pass 2: y, [64][6]
+struct SensShared : RiccatiShared {
   double nu[65 * 12];        // load on stage k's z row for dx_0 column i, [k][i]
   int zidx[65];
 };
@@ -126,79 +73,22 @@ __global__ void __launch_bounds__(64) sens_kernel(SensArgs a) {
   const int lane = threadIdx.x;
   const int N = a.N, ns = a.n_stages;
   const double dt = a.dt, dtm = a.dt / a.m;
-  const bool st = lane < N;          // this lane owns a stage
-  const int k = st ? lane : N - 1;   // clamped: loads stay in bounds
   const bool colane = lane < 12;     // this lane owns a column of P / of S
   const int col = colane ? lane : 0;
 
   for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
     const double mu = a.mu ? a.mu[b] : a.mu_default;
-    const double tol = a.act_tol;
     // ------------------------------------------------------------ pass 0
-    const double* xl = a.x_lin + (b * (N + 1) + k) * 12;
-    const double* pfp = a.pf + (b * N + k) * 3;
-    double u[6], cs[2], bw[18];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) u[c] = a.u[(b * N + k) * 6 + c];
-    const bool stance = a.C[b * N + k] != 0.0;
-    {
-      const double p[3] = {xl[0], xl[1], xl[2]};
-      const double pfk[3] = {pfp[0], pfp[1], pfp[2]};
-      stage_dynamics_vals<VAR, double>(0, xl[5], p, pfk, a.Jinv, a.rh, dt, cs, bw);
-    }
-    // z row of this stage (stage 0 sits on the fixed x_0)
-    const double zslack = a.x[(b * (N + 1) + k) * 12 + 2] - kZmin;
-    const bool zact = st && lane >= 1 && zslack <= tol * (1.0 + kZmin);
-    double tm[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const double lim = tau_lim(3 + c);
-      const bool pin = lim - u[3 + c] <= tol * (1.0 + lim) || u[3 + c] + lim <= tol * (1.0 + lim);
-      tm[c] = pin ? 0.0 : 1.0;
-    }
-    // forces: stage class, active rows and projector, branch-free (selects).
-    // Swing, and stance with fz = 0 (five dependent rows of rank 3): pinned.
-    const bool reg = stance && !(u[2] <= tol);
-    double pi[6];
-    {
-      const double s0 = mu * u[2] - u[0], s1 = mu * u[2] + u[0];
-      const double s2 = mu * u[2] - u[1], s3 = mu * u[2] + u[1];
-      const bool a3 = s0 <= tol, a4 = s1 <= tol, a5 = s2 <= tol, a6 = s3 <= tol;
-      const bool xp = a3 && (!a4 || s0 <= s1);
-      const bool yp = a5 && (!a6 || s2 <= s3);
-      int fm = xp ? A_FXP : (a4 ? A_FXM : 0);
-      if (VAR == 3) fm |= yp ? A_FYP : (a6 ? A_FYM : 0);
-      fm |= (kFzMax - u[2] <= tol * (1.0 + kFzMax)) ? A_FZU : 0;
-      // both signs of a pair active while fz > tol (mu < 1, fz <= tol / mu): the pair
-      // spans (e_axis, e_z), which the kept row and a pinned fz span as well
-      fm |= ((a3 && a4) || (VAR == 3 && a5 && a6)) ? A_FZU : 0;
-      force_projector<VAR>(reg ? fm : 0, mu, pi);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) pi[i] = reg ? pi[i] : 0.0;
-    }
-    __syncthreads();   // the previous instance's reads of the shared block are done
-    {
-      double* rec = sh.rec + kRec * (st ? lane : 64);   // idle lanes write a spare record
-      rec[R_CS] = cs[0];
-      rec[R_CS + 1] = cs[1];
-#pragma unroll
-      for (int i = 0; i < 18; ++i) rec[R_BW + i] = bw[i];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) rec[R_PI + i] = pi[i];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) rec[R_TM + c] = tm[c];
+    int nq;
+    const int zstage = stage_records<VAR>(a, sh, sh.zidx, b, mu, [&] {
 #pragma unroll
       for (int i = 0; i < 12; ++i) sh.nu[12 * lane + i] = 0.0;
-    }
-    // active z rows -> lanes 0..nq-1, in stage order (nq <= N - 1 <= 63: every row has a lane)
-    const unsigned long long zb = __ballot(zact);
-    const int nq = __popcll(zb);
-    sh.zidx[zact ? __popcll(zb & ((1ull << lane) - 1ull)) : 64] = lane;   // slot 64: spare
-    __syncthreads();
-    const int zi = sh.zidx[lane];   // (unassigned lanes read a stale slot: selected away)
-    const int zstage = lane < nq ? zi : -1;
-
+    }, nq);
     // ------------------------------------------------------------ pass 1
+    // riccati_pass (hmpc_sens_common.h) written out: called as a function, which
+    // reaches the LDS block through a generic reference, this kernel takes one
+    // more VGPR spill (74, 300 B scratch against 73, 296 B) in every form tried
+    // (DESIGN.md 4.8).  Keep the two texts equal.
     double P[12];
 #pragma unroll
     for (int r = 0; r < 12; ++r) P[r] = lane == r ? 2.0 * kTermQ * kQ[r] : 0.0;
@@ -209,7 +99,7 @@ __global__ void __launch_bounds__(64) sens_kernel(SensArgs a) {
       const double* rec = sh.rec + kRec * kk;
       const double cp = rec[R_CS], sp = rec[R_CS + 1];
       double W[6], H[6];
-      bdt_times<VAR>(P, rec, dtm, W);          // column `lane` of Bd'P
+      bdt_times<VAR>(P, rec[R_CS], rec[R_CS + 1], rec + R_BW, dtm, W);   // column `lane` of Bd'P
 #pragma unroll
       for (int c = 0; c < 6; ++c) H[c] = adt_lane(W[c], dt, cp, sp);   // ... of Bd'P Ad
       {
@@ -309,28 +199,13 @@ __global__ void __launch_bounds__(64) sens_kernel(SensArgs a) {
           D0 = fma(y[c], y[c], D0);
         }
         __syncthreads();
-        // own row of W from broadcast reads of the tile, eight columns a block
-#pragma unroll
-        for (int jb = 0; jb < 64; jb += 8) {
-          if (jb < nq) {
-#pragma unroll
-            for (int j = jb; j < jb + 8; ++j) {
-              const double* t = sh.tile + 6 * j;
-              double acc = G[j];
-#pragma unroll
-              for (int c = 0; c < 6; ++c) acc = fma(y[c], t[c], acc);
-              G[j] = acc;
-            }
-          }
-        }
+        gram_row(G, y, sh.tile, nq);   // own row of W
         __syncthreads();
       }
       // W nu = p_0, twelve right-hand sides (the registers of P).  A pivot
       // below the floor: the row is dependent given the pinned inputs (the
       // stage-1 row always is) -- flag it, drop it, its nu stays 0.
-      double rinv_own = 0.0;
-      eliminate(std::make_integer_sequence<int, 64>(), G, P, D0, nq, lane, singular, rinv_own);
-      back_substitute(std::make_integer_sequence<int, 64>(), G, P, nq, lane, rinv_own);
+      solve_rows<12, 0>(G, P, D0, nq, lane, singular);
 #pragma unroll
       for (int i = 0; i < 12; ++i) sh.nu[12 * (zstage >= 0 ? zstage : 64) + i] = P[i];   // row 64: spare
       __syncthreads();

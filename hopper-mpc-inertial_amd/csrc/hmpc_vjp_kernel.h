@@ -44,8 +44,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <utility>
-
 #include "hmpc_internal.h"
 #include "hmpc_model.h"
 #include "hmpc_sens_common.h"
@@ -97,7 +95,7 @@ template <int VAR>
 __device__ __forceinline__ void load_step(const double* rec, const double* cf, const double* Kk, const double* gu,
                                           double w, double dt, double dtm, double (&s)[12], double (&y)[6]) {
   double h[6];
-  bdt_times<VAR>(s, rec, dtm, h);
+  bdt_times<VAR>(s, rec[R_CS], rec[R_CS + 1], rec + R_BW, dtm, h);
 #pragma unroll
   for (int c = 0; c < 6; ++c) {
     h[c] = fma(w, gu[c], h[c]);
@@ -115,53 +113,7 @@ __device__ __forceinline__ void load_step(const double* rec, const double* cf, c
   }
 }
 
-// Step C of the elimination of W nu = rhs, row per lane, one right-hand side:
-// the pivot row comes from lane C by readlane (every register index is a
-// template constant), W's columns in blocks of eight up to nq.
-template <int C>
-__device__ __forceinline__ void eliminate_step(double (&G)[64], double& rhs, double D0, int nq, int lane,
-                                               int& singular, double& rinv_own) {
-  if (C >= nq) return;
-  const double piv = rdlane(G[C], C);
-  const double d0 = rdlane(D0, C);
-  const bool ok = piv > kPivotFloor * d0 && piv > 0.0;
-  const double rinv = ok ? 1.0 / piv : 0.0;
-  singular |= ok ? 0 : 1;
-  rinv_own = lane == C ? rinv : rinv_own;
-  const double f = lane > C ? G[C] * rinv : 0.0;
-  rhs = fma(-f, rdlane(rhs, C), rhs);
-#pragma unroll
-  for (int jb = 0; jb < 64; jb += 8) {
-    if (jb + 7 > C && jb < nq) {
-#pragma unroll
-      for (int j = jb; j < jb + 8; ++j)
-        if (j > C) G[j] = fma(-f, rdlane(G[j], C), G[j]);
-    }
-  }
-}
-template <int... Cs>
-__device__ __forceinline__ void eliminate(std::integer_sequence<int, Cs...>, double (&G)[64], double& rhs, double D0,
-                                          int nq, int lane, int& singular, double& rinv_own) {
-  (eliminate_step<Cs>(G, rhs, D0, nq, lane, singular, rinv_own), ...);
-}
-// nu_C = rhs_C / pivot_C stays in lane C (0 for a dropped row); the rows above take it out
-template <int C>
-__device__ __forceinline__ void back_step(const double (&G)[64], double& rhs, int nq, int lane, double rinv_own) {
-  if (C >= nq) return;
-  const double nc = rdlane(rhs * rinv_own, C);
-  rhs = lane == C ? nc : (lane < C ? fma(-G[C], nc, rhs) : rhs);
-}
-template <int... Cs>
-__device__ __forceinline__ void back_substitute(std::integer_sequence<int, Cs...>, const double (&G)[64], double& rhs,
-                                                int nq, int lane, double rinv_own) {
-  (back_step<63 - Cs>(G, rhs, nq, lane, rinv_own), ...);
-}
-
-struct VjpShared {
-  double rec[65 * kRec];     // one spare record / row / slot for the idle lanes
-  double K[64 * kKst + 8];
-  double cf[64 * kCst];
-  double tile[64 * 6];       // pass 1: Bd'P | Bd'P Ad, [12][6] each; pass 2: y, [64][6]
+struct VjpShared : RiccatiShared {
   double gx[66 * 12];        // g_x[k] until the roll-out, which leaves dx_k in row k >= 1
   double gu[65 * 6];         // g_u[k], then v_k (pass 3), then du_k (roll-out)
   double nu[65];             // load on stage k's z row
@@ -186,173 +138,27 @@ __global__ void __launch_bounds__(64) vjp_kernel(Args a) {
 
   for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
     const double mu = a.mu ? a.mu[b] : a.mu_default;
-    const double tol = a.act_tol;
     // ------------------------------------------------------------ pass 0
-    const double* xl = a.x_lin + (b * (N + 1) + k) * 12;
-    const double* pfp = a.pf + (b * N + k) * 3;
-    double u[6], cs[2], bw[18];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) u[c] = a.u[(b * N + k) * 6 + c];
-    const bool stance = a.C[b * N + k] != 0.0;
-    {
-      const double p[3] = {xl[0], xl[1], xl[2]};
-      const double pfk[3] = {pfp[0], pfp[1], pfp[2]};
-      stage_dynamics_vals<VAR, double>(0, xl[5], p, pfk, a.Jinv, a.rh, dt, cs, bw);
-    }
-    // z row of this stage (stage 0 sits on the fixed x_0)
-    const double zslack = a.x[(b * (N + 1) + k) * 12 + 2] - kZmin;
-    const bool zact = st && lane >= 1 && zslack <= tol * (1.0 + kZmin);
-    double tm[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const double lim = tau_lim(3 + c);
-      const bool pin = lim - u[3 + c] <= tol * (1.0 + lim) || u[3 + c] + lim <= tol * (1.0 + lim);
-      tm[c] = pin ? 0.0 : 1.0;
-    }
-    // forces: stage class, active rows and projector, branch-free (selects).
-    // Swing, and stance with fz = 0 (five dependent rows of rank 3): pinned.
-    const bool reg = stance && !(u[2] <= tol);
-    double pi[6];
-    {
-      const double s0 = mu * u[2] - u[0], s1 = mu * u[2] + u[0];
-      const double s2 = mu * u[2] - u[1], s3 = mu * u[2] + u[1];
-      const bool a3 = s0 <= tol, a4 = s1 <= tol, a5 = s2 <= tol, a6 = s3 <= tol;
-      const bool xp = a3 && (!a4 || s0 <= s1);
-      const bool yp = a5 && (!a6 || s2 <= s3);
-      int fm = xp ? A_FXP : (a4 ? A_FXM : 0);
-      if (VAR == 3) fm |= yp ? A_FYP : (a6 ? A_FYM : 0);
-      fm |= (kFzMax - u[2] <= tol * (1.0 + kFzMax)) ? A_FZU : 0;
-      // both signs of a pair active while fz > tol: the kept row and a pinned fz (4.8)
-      fm |= ((a3 && a4) || (VAR == 3 && a5 && a6)) ? A_FZU : 0;
-      force_projector<VAR>(reg ? fm : 0, mu, pi);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) pi[i] = reg ? pi[i] : 0.0;
-    }
-    __syncthreads();   // the previous instance's reads of the shared block are done
-    {
-      double* rec = sh.rec + kRec * (st ? lane : 64);   // idle lanes write a spare record
-      rec[R_CS] = cs[0];
-      rec[R_CS + 1] = cs[1];
-#pragma unroll
-      for (int i = 0; i < 18; ++i) rec[R_BW + i] = bw[i];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) rec[R_PI + i] = pi[i];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) rec[R_TM + c] = tm[c];
+    int nq;
+    const int zstage = stage_records<VAR>(a, sh, sh.zidx, b, mu, [&] {
       sh.nu[lane] = 0.0;
-    }
-    // the cotangents, flat and coalesced (a NULL one is 0); lanes past the end fill a spare slot
+      // the cotangents, flat and coalesced (a NULL one is 0); lanes past the end fill a spare slot
 #pragma unroll 1
-    for (int i0 = 0; i0 < 12 * (N + 1); i0 += 64) {
-      const int i = i0 + lane;
-      const bool ok = i < 12 * (N + 1);
-      sh.gx[ok ? i : 65 * 12] = a.g_x ? a.g_x[b * (N + 1) * 12 + (ok ? i : 0)] : 0.0;
-    }
+      for (int i0 = 0; i0 < 12 * (N + 1); i0 += 64) {
+        const int i = i0 + lane;
+        const bool ok = i < 12 * (N + 1);
+        sh.gx[ok ? i : 65 * 12] = a.g_x ? a.g_x[b * (N + 1) * 12 + (ok ? i : 0)] : 0.0;
+      }
 #pragma unroll 1
-    for (int i0 = 0; i0 < 6 * N; i0 += 64) {
-      const int i = i0 + lane;
-      const bool ok = i < 6 * N;
-      sh.gu[ok ? i : 64 * 6] = a.g_u ? a.g_u[b * N * 6 + (ok ? i : 0)] : 0.0;
-    }
-    // active z rows -> lanes 0..nq-1, in stage order (nq <= N - 1 <= 63: the base lane nq exists)
-    const unsigned long long zb = __ballot(zact);
-    const int nq = __popcll(zb);
-    sh.zidx[zact ? __popcll(zb & ((1ull << lane) - 1ull)) : 64] = lane;   // slot 64: spare
-    __syncthreads();
-    const int zi = sh.zidx[lane];   // (unassigned lanes read a stale slot: selected away)
-    const int zstage = lane < nq ? zi : -1;
-
+      for (int i0 = 0; i0 < 6 * N; i0 += 64) {
+        const int i = i0 + lane;
+        const bool ok = i < 6 * N;
+        sh.gu[ok ? i : 64 * 6] = a.g_u ? a.g_u[b * N * 6 + (ok ? i : 0)] : 0.0;
+      }
+    }, nq);   // (nq <= N - 1 <= 63: the base lane nq exists)
     // ------------------------------------------------------------ pass 1
+    riccati_pass<VAR>(sh, N, dt, dtm);
     double P[12];
-#pragma unroll
-    for (int r = 0; r < 12; ++r) P[r] = lane == r ? 2.0 * kTermQ * kQ[r] : 0.0;
-    double* tW = sh.tile;
-    double* tH = sh.tile + 72;
-#pragma unroll 1
-    for (int kk = N - 1; kk >= 0; --kk) {
-      const double* rec = sh.rec + kRec * kk;
-      const double cp = rec[R_CS], sp = rec[R_CS + 1];
-      double W[6], H[6];
-      bdt_times<VAR>(P, rec, dtm, W);          // column `lane` of Bd'P
-#pragma unroll
-      for (int c = 0; c < 6; ++c) H[c] = adt_lane(W[c], dt, cp, sp);   // ... of Bd'P Ad
-      {
-        const int slot = colane ? 6 * lane : 144;   // idle lanes: spare slots past both tiles
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-          tW[slot + c] = W[c];
-          tH[slot + c] = H[c];
-        }
-      }
-      __syncthreads();
-      // G = 2 lambda R + Bd'P Bd (rows 6..11 of Bd), then G~ = Pi G Pi + (I - Pi)
-      double Gm[6][6];
-      const double r2 = kk == N - 1 ? 0.0 : 2.0 * kRdiag;
-#pragma unroll
-      for (int c = 0; c < 6; ++c)
-#pragma unroll
-        for (int d = 0; d <= c; ++d) {
-          double acc = c == d ? r2 : 0.0;
-          if (d < 3) {
-#pragma unroll
-            for (int r = 0; r < 3; ++r) acc = fma(tW[6 * (6 + r) + c], bv<VAR>(r, d, dtm, cp, sp), acc);
-          }
-#pragma unroll
-          for (int r = 0; r < 3; ++r) acc = fma(tW[6 * (9 + r) + c], rec[R_BW + 6 * r + d], acc);
-          Gm[c][d] = acc;
-          Gm[d][c] = acc;
-        }
-#pragma unroll
-      for (int r = 0; r < 6; ++r) pi_apply(rec + R_PI, Gm[r]);   // rows of G Pi (G is symmetric)
-#pragma unroll
-      for (int c = 0; c < 6; ++c) {
-        double v[6];
-#pragma unroll
-        for (int r = 0; r < 6; ++r) v[r] = Gm[r][c];
-        pi_apply(rec + R_PI, v);
-#pragma unroll
-        for (int r = 0; r < 6; ++r) Gm[r][c] = v[r];
-      }
-      Gm[0][0] += 1.0 - rec[R_PI + 0];
-      Gm[1][0] -= rec[R_PI + 1];
-      Gm[2][0] -= rec[R_PI + 2];
-      Gm[1][1] += 1.0 - rec[R_PI + 3];
-      Gm[2][1] -= rec[R_PI + 4];
-      Gm[2][2] += 1.0 - rec[R_PI + 5];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) Gm[3 + c][3 + c] += 1.0 - rec[R_TM + c];
-      double cf[kCst];
-      chol6(Gm, cf);
-#pragma unroll
-      for (int i = 0; i < kCst; ++i) sh.cf[kCst * kk + i] = cf[i];   // every lane, the same values
-      // column `lane` of K = -Pi G~^-1 Pi (Bd'P Ad)
-      double Kc[6];
-#pragma unroll
-      for (int c = 0; c < 6; ++c) Kc[c] = H[c];
-      pi_apply(rec + R_PI, Kc);
-      chol_fwd(cf, Kc);
-      chol_bwd(cf, Kc);
-      pi_apply(rec + R_PI, Kc);
-#pragma unroll
-      for (int c = 0; c < 6; ++c) {
-        Kc[c] = -Kc[c];
-        sh.K[colane ? kKst * kk + 12 * c + lane : 64 * kKst + c] = Kc[c];   // idle lanes: the spare slots
-      }
-      // P <- 2 Q + Ad'P Ad + (Bd'P Ad)' K
-      if (kk > 0) {
-#pragma unroll
-        for (int r = 0; r < 12; ++r) P[r] = adt_lane(P[r], dt, cp, sp);   // P Ad
-        adt_times(P, dt, cp, sp);
-#pragma unroll
-        for (int r = 0; r < 12; ++r) {
-          double acc = P[r];
-#pragma unroll
-          for (int c = 0; c < 6; ++c) acc = fma(tH[6 * r + c], Kc[c], acc);
-          P[r] = acc + (lane == r ? 2.0 * kQ[r] : 0.0);
-        }
-      }
-      __syncthreads();
-    }
 
     // ------------------------------------------------------------ pass 2
     // The loaded LQR's optimal value is -1/2 |y0 + Y nu|^2 summed over the stages
@@ -366,7 +172,7 @@ __global__ void __launch_bounds__(64) vjp_kernel(Args a) {
       const double base = lane == nq ? 1.0 : 0.0;
 #pragma unroll
       for (int r = 0; r < 12; ++r) P[r] = base * sh.gx[12 * N + r];
-      double D0 = 0.0, rhs = 0.0;
+      double D0 = 0.0, rhs[1] = {0.0};
 #pragma unroll 1
       for (int kk = N - 1; kk >= 0; --kk) {
         load_step<VAR>(sh.rec + kRec * kk, sh.cf + kCst * kk, sh.K + kKst * kk, sh.gu + 6 * kk, base, dt, dtm, P, y);
@@ -379,34 +185,19 @@ __global__ void __launch_bounds__(64) vjp_kernel(Args a) {
           D0 = fma(y[c], y[c], D0);
         }
         __syncthreads();
-        // own row of W from broadcast reads of the tile, eight columns a block
-#pragma unroll
-        for (int jb = 0; jb < 64; jb += 8) {
-          if (jb < nq) {
-#pragma unroll
-            for (int j = jb; j < jb + 8; ++j) {
-              const double* t = sh.tile + 6 * j;
-              double acc = G[j];
-#pragma unroll
-              for (int c = 0; c < 6; ++c) acc = fma(y[c], t[c], acc);
-              G[j] = acc;
-            }
-          }
-        }
+        gram_row(G, y, sh.tile, nq);   // own row of W
         {
           const double* t = sh.tile + 6 * nq;   // the base lane's y
 #pragma unroll
-          for (int c = 0; c < 6; ++c) rhs = fma(y[c], t[c], rhs);
+          for (int c = 0; c < 6; ++c) rhs[0] = fma(y[c], t[c], rhs[0]);
         }
         __syncthreads();
       }
       // A pivot below the floor: the row is dependent given the pinned inputs
       // (the stage-1 row always is) -- flag it, drop it, its nu stays 0.
-      rhs = -rhs;
-      double rinv_own = 0.0;
-      eliminate(std::make_integer_sequence<int, 64>(), G, rhs, D0, nq, lane, singular, rinv_own);
-      back_substitute(std::make_integer_sequence<int, 64>(), G, rhs, nq, lane, rinv_own);
-      sh.nu[zstage >= 0 ? zstage : 64] = rhs;   // slot 64: spare
+      rhs[0] = -rhs[0];
+      solve_rows<1, 0>(G, rhs, D0, nq, lane, singular);
+      sh.nu[zstage >= 0 ? zstage : 64] = rhs[0];   // slot 64: spare
       __syncthreads();
     }
 

@@ -211,16 +211,10 @@ struct LinEpilogue {
       if (lane < 12) sh.K[12 * N + lane] = 0.0;
     }
     if (a.grad_mu) {
-      // the stage class and the held friction rows by pass 0's rule
-      const bool stance = a.C[b * N + k] != 0.0;
-      const bool reg = stance && !(u[2] <= tol);
-      const double s0 = mu * u[2] - u[0], s1 = mu * u[2] + u[0];
-      const double s2 = mu * u[2] - u[1], s3 = mu * u[2] + u[1];
-      const bool a3 = s0 <= tol, a4 = s1 <= tol, a5 = s2 <= tol, a6 = s3 <= tol;
-      const bool xp = a3 && (!a4 || s0 <= s1);
-      const bool yp = a5 && (!a6 || s2 <= s3);
-      const bool both = (a3 && a4) || (VAR == 3 && a5 && a6);   // fz pinned at ~0: nothing moves with mu
-      const bool live = st && reg && !both;
+      // the stage class and the held friction rows: pass 0's
+      const StageClass sc =
+          classify_stage<VAR>(u, a.x[(b * (N + 1) + k) * 12 + 2], a.C[b * N + k] != 0.0, mu, tol);
+      const bool live = st && sc.reg && !both_signs<VAR>(sc);   // both signs: fz pinned at ~0, nothing moves with mu
       const double r2 = k == N - 1 ? 0.0 : 2.0 * kRdiag;
       const double* lam = a.lam + (b * N + k) * 11;
       double acc = 0.0;
@@ -232,7 +226,7 @@ struct LinEpilogue {
         else rho += bv<VAR>(0, ax, dtm, cp, sp) * v1[0] + bv<VAR>(1, ax, dtm, cp, sp) * v1[1];
 #pragma unroll
         for (int r = 0; r < 3; ++r) rho = fma(rec[R_BW + 6 * r + ax], w1[r], rho);
-        const bool plus = ax == 0 ? xp : yp, held = ax == 0 ? (a3 || a4) : (a5 || a6);
+        const bool plus = ax == 0 ? sc.xp : sc.yp, held = ax == 0 ? (sc.a3 || sc.a4) : (sc.a5 || sc.a6);
         const double lm = plus ? lam[3 + 2 * ax] : lam[4 + 2 * ax];
         const double sg = plus ? 1.0 : -1.0;
         acc += (live && held) ? fma(sg * rho, u[2], -lm * du[2]) : 0.0;

@@ -269,6 +269,35 @@ class Context:
         self._check(rc, 'hmpc_solve_batch_stats')
         return out
 
+    def _point_args(self, x_in, x_lin, x_ref, pf, C, u, x, mu, stream, optional=(), grads=None, want=(),
+                    out=None):
+        """What kkt_device, sens_device, vjp_device and vjp_lin_device share: the
+        check of the primal point and its problem data, of mu and of the further
+        optional tensors `optional` ((tensor, shape, name), ...), and the stream
+        handle.  With `grads` (name -> shape) also the gradient outputs of the
+        two vjp methods: allocated for the names in `want` when `out` is None,
+        then checked.  Returns (out, stream handle)."""
+        import torch
+        N = self.N
+        B = x_in.shape[0]
+        for t_, shp, nm in ((x_in, (B, 12), 'x_in'), (x_lin, (B, N + 1, 12), 'x_lin'),
+                            (x_ref, (B, N, 12), 'x_ref'), (pf, (B, N, 3), 'pf'), (C, (B, N), 'C'),
+                            (u, (B, N, 6), 'u'), (x, (B, N + 1, 12), 'x')):
+            _check_tensor(t_, shp, nm, self.device)
+        for t_, shp, nm in ((mu, (B,), 'mu'),) + tuple(optional):
+            _check_tensor(t_, shp, nm, self.device, optional=True)
+        if grads is not None:
+            if out is None:
+                dev = x_in.device
+                out = {k: torch.empty(grads[k], dtype=torch.float64, device=dev) if k in want else None
+                       for k in grads}
+                out['flags'] = torch.empty(B, dtype=torch.int32, device=dev)
+            for k, shp in grads.items():
+                _check_tensor(out.get(k), shp, f"out['{k}']", self.device, optional=True)
+            _check_tensor(out.get('flags'), (B,), "out['flags']", self.device, dtype='int32', optional=True)
+        s = stream if stream is not None else torch.cuda.current_stream(x_in.device).cuda_stream
+        return out, s
+
     def kkt_device(self, x_in, x_lin, x_ref, pf, C, u, x, mu=None, act_tol=1e-8, out=None, stream=None):
         """Multipliers and KKT certificate of the primal point (x, u)
         (hmpc_kkt_batch): nu (B,N), lam (B,N,11), cert (B,5) = primal_eq,
@@ -277,11 +306,7 @@ class Context:
         import torch
         N = self.N
         B = x_in.shape[0]
-        for t_, shp, nm in ((x_in, (B, 12), 'x_in'), (x_lin, (B, N + 1, 12), 'x_lin'),
-                            (x_ref, (B, N, 12), 'x_ref'), (pf, (B, N, 3), 'pf'), (C, (B, N), 'C'),
-                            (u, (B, N, 6), 'u'), (x, (B, N + 1, 12), 'x')):
-            _check_tensor(t_, shp, nm, self.device)
-        _check_tensor(mu, (B,), 'mu', self.device, optional=True)
+        _, s = self._point_args(x_in, x_lin, x_ref, pf, C, u, x, mu, stream)
         if out is None:
             dev = x_in.device
             out = dict(nu=torch.empty((B, N), dtype=torch.float64, device=dev),
@@ -292,7 +317,6 @@ class Context:
         _check_tensor(out.get('lam'), (B, N, 11), "out['lam']", self.device, optional=True)
         _check_tensor(out.get('cert'), (B, 5), "out['cert']", self.device)
         _check_tensor(out.get('flags'), (B,), "out['flags']", self.device, dtype='int32', optional=True)
-        s = stream if stream is not None else torch.cuda.current_stream(x_in.device).cuda_stream
         rc = self._lib.hmpc_kkt_batch(self._h, B, _ptr(x_in), _ptr(x_lin), _ptr(x_ref), _ptr(pf), _ptr(C),
                                       _ptr(mu), _ptr(u), _ptr(x), float(act_tol), _ptr(out.get('nu')),
                                       _ptr(out.get('lam')), _ptr(out['cert']), _ptr(out.get('flags')),
@@ -310,18 +334,13 @@ class Context:
         N = self.N
         B = x_in.shape[0]
         ns = N if n_stages is None else int(n_stages)
-        for t_, shp, nm in ((x_in, (B, 12), 'x_in'), (x_lin, (B, N + 1, 12), 'x_lin'),
-                            (x_ref, (B, N, 12), 'x_ref'), (pf, (B, N, 3), 'pf'), (C, (B, N), 'C'),
-                            (u, (B, N, 6), 'u'), (x, (B, N + 1, 12), 'x')):
-            _check_tensor(t_, shp, nm, self.device)
-        _check_tensor(mu, (B,), 'mu', self.device, optional=True)
+        _, s = self._point_args(x_in, x_lin, x_ref, pf, C, u, x, mu, stream)
         if out is None:
             dev = x_in.device
             out = dict(S=torch.empty((B, max(ns, 0), 6, 12), dtype=torch.float64, device=dev),
                        flags=torch.empty(B, dtype=torch.int32, device=dev))
         _check_tensor(out.get('S'), (B, max(ns, 0), 6, 12), "out['S']", self.device)
         _check_tensor(out.get('flags'), (B,), "out['flags']", self.device, dtype='int32', optional=True)
-        s = stream if stream is not None else torch.cuda.current_stream(x_in.device).cuda_stream
         rc = self._lib.hmpc_sens_batch(self._h, B, _ptr(x_in), _ptr(x_lin), _ptr(x_ref), _ptr(pf), _ptr(C),
                                        _ptr(mu), _ptr(u), _ptr(x), float(act_tol), ns, _ptr(out['S']),
                                        _ptr(out.get('flags')), ctypes.c_void_p(s))
@@ -336,24 +355,11 @@ class Context:
         inputs named in `want`: x_in (B,12), x_ref (B,N,12), pf (B,N,3), and
         flags (B,) (VJP_SINGULAR).  An input not in `want` is None in the result.
         Inputs as sens_device; async on `stream`."""
-        import torch
         N = self.N
         B = x_in.shape[0]
-        for t_, shp, nm in ((x_in, (B, 12), 'x_in'), (x_lin, (B, N + 1, 12), 'x_lin'),
-                            (x_ref, (B, N, 12), 'x_ref'), (pf, (B, N, 3), 'pf'), (C, (B, N), 'C'),
-                            (u, (B, N, 6), 'u'), (x, (B, N + 1, 12), 'x')):
-            _check_tensor(t_, shp, nm, self.device)
-        for t_, shp, nm in ((mu, (B,), 'mu'), (g_u, (B, N, 6), 'g_u'), (g_x, (B, N + 1, 12), 'g_x')):
-            _check_tensor(t_, shp, nm, self.device, optional=True)
-        shapes = dict(x_in=(B, 12), x_ref=(B, N, 12), pf=(B, N, 3))
-        if out is None:
-            dev = x_in.device
-            out = {k: torch.empty(shapes[k], dtype=torch.float64, device=dev) if k in want else None for k in shapes}
-            out['flags'] = torch.empty(B, dtype=torch.int32, device=dev)
-        for k, shp in shapes.items():
-            _check_tensor(out.get(k), shp, f"out['{k}']", self.device, optional=True)
-        _check_tensor(out.get('flags'), (B,), "out['flags']", self.device, dtype='int32', optional=True)
-        s = stream if stream is not None else torch.cuda.current_stream(x_in.device).cuda_stream
+        out, s = self._point_args(x_in, x_lin, x_ref, pf, C, u, x, mu, stream,
+                                  optional=((g_u, (B, N, 6), 'g_u'), (g_x, (B, N + 1, 12), 'g_x')),
+                                  grads=dict(x_in=(B, 12), x_ref=(B, N, 12), pf=(B, N, 3)), want=want, out=out)
         rc = self._lib.hmpc_vjp_batch(self._h, B, _ptr(x_in), _ptr(x_lin), _ptr(x_ref), _ptr(pf), _ptr(C),
                                       _ptr(mu), _ptr(u), _ptr(x), float(act_tol), _ptr(g_u), _ptr(g_x),
                                       _ptr(out.get('x_in')), _ptr(out.get('x_ref')), _ptr(out.get('pf')),
@@ -367,28 +373,16 @@ class Context:
         and 5 can be non-zero) and mu (B,) as well (hmpc_vjp_lin_batch).  nu (B,N)
         and lam (B,N,11) are the primal point's multipliers as kkt_device returns
         them; when either is None both are fetched by a kkt_device call on `stream`."""
-        import torch
         N = self.N
         B = x_in.shape[0]
-        for t_, shp, nm in ((x_in, (B, 12), 'x_in'), (x_lin, (B, N + 1, 12), 'x_lin'),
-                            (x_ref, (B, N, 12), 'x_ref'), (pf, (B, N, 3), 'pf'), (C, (B, N), 'C'),
-                            (u, (B, N, 6), 'u'), (x, (B, N + 1, 12), 'x')):
-            _check_tensor(t_, shp, nm, self.device)
-        for t_, shp, nm in ((mu, (B,), 'mu'), (g_u, (B, N, 6), 'g_u'), (g_x, (B, N + 1, 12), 'g_x'),
-                            (nu, (B, N), 'nu'), (lam, (B, N, 11), 'lam')):
-            _check_tensor(t_, shp, nm, self.device, optional=True)
-        shapes = dict(x_in=(B, 12), x_ref=(B, N, 12), pf=(B, N, 3), x_lin=(B, N + 1, 12), mu=(B,))
-        if out is None:
-            dev = x_in.device
-            out = {k: torch.empty(shapes[k], dtype=torch.float64, device=dev) if k in want else None for k in shapes}
-            out['flags'] = torch.empty(B, dtype=torch.int32, device=dev)
-        for k, shp in shapes.items():
-            _check_tensor(out.get(k), shp, f"out['{k}']", self.device, optional=True)
-        _check_tensor(out.get('flags'), (B,), "out['flags']", self.device, dtype='int32', optional=True)
+        out, s = self._point_args(x_in, x_lin, x_ref, pf, C, u, x, mu, stream,
+                                  optional=((g_u, (B, N, 6), 'g_u'), (g_x, (B, N + 1, 12), 'g_x'),
+                                            (nu, (B, N), 'nu'), (lam, (B, N, 11), 'lam')),
+                                  grads=dict(x_in=(B, 12), x_ref=(B, N, 12), pf=(B, N, 3), x_lin=(B, N + 1, 12),
+                                             mu=(B,)), want=want, out=out)
         if nu is None or lam is None:
             kkt = self.kkt_device(x_in, x_lin, x_ref, pf, C, u, x, mu=mu, act_tol=act_tol, stream=stream)
             nu, lam = kkt['nu'], kkt['lam']
-        s = stream if stream is not None else torch.cuda.current_stream(x_in.device).cuda_stream
         rc = self._lib.hmpc_vjp_lin_batch(self._h, B, _ptr(x_in), _ptr(x_lin), _ptr(x_ref), _ptr(pf), _ptr(C),
                                           _ptr(mu), _ptr(u), _ptr(x), float(act_tol), _ptr(nu), _ptr(lam),
                                           _ptr(g_u), _ptr(g_x), _ptr(out.get('x_in')), _ptr(out.get('x_ref')),

@@ -134,6 +134,27 @@ def test_swing_budget(kernels):
     assert sw['.sgpr_spill_count'] <= 8   # (the sweep masks stay out of the loop: 196 when hoisted)
 
 
+POST_SOLVE = {   # kernel: (LDS bytes, {variant: (scratch B/lane, VGPR spills)}), DESIGN.md 4.7-4.10
+    '10kkt_kernelILi{v}EEEvNS_7KktArgsE': (34528, {2: (0, 0), 3: (0, 0)}),
+    '11sens_kernelILi{v}EEEvNS_8SensArgsE': (72336, {2: (296, 73), 3: (296, 73)}),
+    '10vjp_kernelILi{v}ENS_7VjpArgsENS0_10NoEpilogueEEEvT0_': (76072, {2: (508, 126), 3: (500, 124)}),
+    '10vjp_kernelILi{v}ENS_10VjpLinArgsENS0_11LinEpilogueEEEvT0_': (76072, {2: (584, 147), 3: (616, 159)}),
+}
+
+
+@pytest.mark.parametrize('v', [3, 2])
+def test_post_solve_budgets(kernels, v):
+    # the kernels that share csrc/hmpc_sens_common.h: their LDS blocks are exact
+    # (two workgroups per CU for sens / vjp), scratch and VGPR spills may not grow
+    # past the figures of the build before the header became their single source
+    for name, (lds, fig) in POST_SOLVE.items():
+        (k,) = kernels['_ZN4hmpc12_GLOBAL__N_1' + name.format(v=v)]
+        scratch, spills = fig[v]
+        assert k['.group_segment_fixed_size'] == lds, name
+        assert k['.private_segment_fixed_size'] <= scratch, name
+        assert k['.vgpr_spill_count'] <= spills, name
+
+
 def test_riccati_budgets(kernels):
     # the Runner's horizon: the factorisation kernel (3 waves / SIMD, no
     # spill), then the solve kernel without phase 2 (1 wave / SIMD)
