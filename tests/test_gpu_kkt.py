@@ -50,12 +50,37 @@ CASES += [('3f', 2, IDX['3f'], 'per_stage', 'stage1'), ('2f', 10, IDX['2f'], 'pe
 IDS = ['-'.join(map(str, (c[0], c[1], len(c[2]), c[3], c[4]))) for c in CASES]
 
 
-def ctx_for(variant, N, uref='aliased'):
-    import hmpc
+def constants(consts=None):
+    """dict(t, m, g, Jinv, rh): the Runner's, or those of the hashable
+    (t, m, g, Jinv[9] row-major, rh[3]) that the references below take as `consts`."""
     from oracle import hmpc_oracle as ho
+    if consts is None:
+        return ho.runner_constants()
+    t, m, g, Jinv, rh = consts
+    return dict(t=t, m=m, g=g, Jinv=np.array(Jinv, dtype=np.float64).reshape(3, 3), rh=np.array(rh, dtype=np.float64))
+
+
+def mpc_params(variant, N, mu, consts=None):
+    from oracle import hmpc_oracle as ho
+    c = constants(consts)
+    return ho.MpcParams(variant=variant, N=N, t=c['t'], m=c['m'], g=c['g'], mu=mu, Jinv=c['Jinv'], rh=c['rh'])
+
+
+def windows(variant, N, idx):
+    """The recorded golden windows (N <= 10, truncated to N) or hmpc_plan's sampler (longer horizons)."""
+    import hmpc_plan
+    if N > 10:
+        d = hmpc_plan.sample_instances(max(idx) + 1, N, curve=True, seed=64)
+    else:
+        d = np.load(os.path.join(GOLDEN, f'qp_{variant}_N10_straight.npz'))
+    return {k: np.array(d[k][list(idx)], dtype=np.float64) for k in ('x_in', 'x_lin', 'x_ref', 'pf', 'C', 'mu')}
+
+
+def ctx_for(variant, N, uref='aliased', consts=None):
+    import hmpc
     if not torch.cuda.is_available():
         pytest.fail('GPU tests need an MI355X (torch.cuda.is_available() is False)')
-    c = ho.runner_constants()
+    c = constants(consts)
     return hmpc.Context(variant, N, t=c['t'], m=c['m'], g=c['g'], mu=1.0, Jinv=c['Jinv'], rh=c['rh'],
                         uref_mode=uref)
 
@@ -86,20 +111,15 @@ def oracle_duals(variant, N, C, y):
 
 
 @functools.lru_cache(maxsize=None)
-def reference(variant, N, idx, uref, mode):
+def reference(variant, N, idx, uref, mode, consts=None):
     """Inputs [B, ...], the oracle's primal, duals and certificate, and the
     instances expected singular (computed once, shared by the tests)."""
-    import hmpc_plan
     from oracle import hmpc_oracle as ho
-    if N == 64:
-        d = hmpc_plan.sample_instances(max(idx) + 1, N, curve=True, seed=64)
-    else:
-        d = np.load(os.path.join(GOLDEN, f'qp_{variant}_N10_straight.npz'))
-    inst = {k: np.array(d[k][list(idx)], dtype=np.float64) for k in ('x_in', 'x_lin', 'x_ref', 'pf', 'C', 'mu')}
+    inst = windows(variant, N, idx)
     inst['x_lin'] = inst['x_lin'][:, :N + 1]
     for k in ('x_ref', 'pf', 'C'):
         inst[k] = np.ascontiguousarray(inst[k][:, :N])
-    z0, vz, zref = {'plain': (None,) * 3, 'drop': (0.14, -1.0, 0.05), 'zref': (None, None, 0.05),
+    z0, vz, zref = {'plain': (None,) * 3, 'drop': (0.14, -1.0, 0.05), 'drop6': (0.14, -0.6, 0.05), 'zref': (None, None, 0.05),
                     'ride': (0.104, -0.1, -2.0), 'stage1': (0.102, -0.1, 0.05)}[mode]
     if z0 is not None:
         inst['x_in'][:, 2], inst['x_in'][:, 8] = z0, vz
@@ -110,7 +130,7 @@ def reference(variant, N, idx, uref, mode):
     inst['x_lin'][:, 0] = inst['x_in']
     ref = dict(u=[], x=[], nu=[], lam=[], cert=[])
     for i in range(len(idx)):
-        p = ho.MpcParams.runner(variant, N, mu=float(inst['mu'][i]))
+        p = mpc_params(variant, N, float(inst['mu'][i]), consts)
         s = ho.solve_instance(p, inst['x_in'][i], inst['x_lin'][i], inst['x_ref'][i], inst['pf'][i],
                               inst['C'][i], uref)
         assert s['status'] == 'solved', (variant, N, idx[i], mode)   # the batch keeps its size
@@ -160,9 +180,9 @@ def test_inputs_cover_the_classes():
 
 
 @pytest.mark.parametrize('variant,N,idx,uref,mode', CASES, ids=IDS)
-def test_duals_from_the_exact_primal(variant, N, idx, uref, mode):
-    inst, ref = reference(variant, N, idx, uref, mode)
-    r = run_kkt(ctx_for(variant, N, uref), inst, ref['u'], ref['x'])
+def test_duals_from_the_exact_primal(variant, N, idx, uref, mode, consts=None):
+    inst, ref = reference(variant, N, idx, uref, mode, consts)
+    r = run_kkt(ctx_for(variant, N, uref, consts), inst, ref['u'], ref['x'])
     assert np.array_equal(r['flags'] != 0, ref['singular'])
     ok = ~ref['singular']   # flagged instances: the certificate only
     apex = (inst['C'] != 0) & (np.abs(ref['u'][:, :, 2]) <= 1e-8)

@@ -20,6 +20,8 @@ from conftest import DENSE10_3F_LPT
 
 torch = pytest.importorskip('torch')
 
+from test_gpu_kkt import mpc_params   # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 U_TOL = 1e-6
@@ -44,10 +46,10 @@ def adversarial(B, N, seed, wscale, vscale, mu=0.3):
     return inst
 
 
-def active_rows(N, inst, ref, i):
+def active_rows(N, inst, ref, i, consts=None):
     """Inequality rows of the reference-built QP active at the port's optimum."""
     from oracle import hmpc_oracle as ho
-    p = ho.MpcParams.runner('3f', N, mu=float(inst['mu'][i]))
+    p = mpc_params('3f', N, float(inst['mu'][i]), consts)
     _, _, Gd = ho.constant_matrices(p)
     Ad, Bd = ho.gen_dt_dynamics(p, inst['x_lin'][i], inst['pf'][i])
     qp = ho.build_qp(p, inst['x_in'][i], inst['x_ref'][i], Ad, Bd, Gd, inst['C'][i])

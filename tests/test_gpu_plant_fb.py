@@ -82,8 +82,8 @@ def gpu_fb(ctx, X0, U, K, x_nom, pf, C0, mu, n, flags, layout, c):
 
 
 @pytest.mark.parametrize('n,B,flags,layout', CASES, ids=[f'{c[0]}-{c[1]}-{c[2]}-{c[3]}' for c in CASES])
-def test_against_reference(n, B, flags, layout):
-    c, fy0 = consts(), layout == '2f'
+def test_against_reference(n, B, flags, layout, cset=None):
+    c, fy0 = consts(cset), layout == '2f'
     X0, U, K, x_nom, pf, C0, mu = case_inputs(n, B, flags, layout)
     Xh, Uh, xo, sat, raw, moves, yaws = fb_ref(X0, U, K, x_nom, pf, C0, mu, n, flags, fy0, c)
     # on the reference alone: no clip move and no yaw difference near where sat or the wrap could flip on rounding
@@ -94,7 +94,7 @@ def test_against_reference(n, B, flags, layout):
         assert (v[st, 0] < r[st, 0]).any() and (v[st, 0] > r[st, 0]).any() and not sat.all()
     if layout == 'yaw':
         assert yaws[0] > 6 and yaws[n] < -6
-    X, got = gpu_fb(ctx_for('2f' if fy0 else '3f', 10), X0, U, K, x_nom, pf, C0, mu, n, flags, layout, c)
+    X, got = gpu_fb(ctx_for('2f' if fy0 else '3f', 10, cset), X0, U, K, x_nom, pf, C0, mu, n, flags, layout, c)
     d = dict(X=figure(X, Xh[:, -1]), X_hist=figure(got['X_hist'], Xh), x_out=figure(got['x_out'], xo),
              U_hist=figure(got['U_hist'], Uh))
     print(f'PFB1 n={n} B={B} flags={flags} {layout} ' + ' '.join(f'{k}={v:.3e}' for k, v in d.items())

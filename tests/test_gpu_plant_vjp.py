@@ -9,6 +9,7 @@ import pytest
 
 torch = pytest.importorskip('torch')
 
+from test_gpu_kkt import constants   # noqa: E402
 from test_gpu_vjp_lin import IDX, bound, ctx_for, mpcontrol_chain, reference   # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -19,9 +20,10 @@ CASES = [(0, 3, 'x', 'dense'), (1, 1, 'X', 'dense'), (1, 65, 'x', 'dense'), (2, 
          (20, 130, 'Xxh', 'dense'), (3, 4, 'h', 'dense'), (3, 5, 'Xxh', 'shared')]
 
 
-def consts():
-    from oracle import hmpc_oracle as ho
-    return ho.runner_constants()
+def consts(c=None):
+    """m, g, J, Jinv, rh of the plant: the Runner's, or those of test_gpu_kkt.constants(c) with J = inv(Jinv)"""
+    c = constants(c)
+    return dict(c, J=c['J'] if 'J' in c else np.linalg.inv(c['Jinv']))
 
 
 mv = lambda M, a: (M @ a[..., None])[..., 0]   # noqa: E731
@@ -123,9 +125,9 @@ def figure(got, ref):
 
 
 @pytest.mark.parametrize('n,B,cots,layout', CASES, ids=[f'{c[0]}-{c[1]}-{c[2]}-{c[3]}' for c in CASES])
-def test_gradients(n, B, cots, layout):
+def test_gradients(n, B, cots, layout, cset=None):
     from oracle import hmpc_plant as pl
-    c = consts()
+    c = consts(cset)
     X0, U, pf, g = inputs(n, B, 100 * n + B)
     if layout == 'shared':
         pf = np.repeat(pf[:1], B, 0)   # the dense layout of the shared plan: the reference's
@@ -136,7 +138,7 @@ def test_gradients(n, B, cots, layout):
             Xr = pl.rk4_normalized(Xr, U[b], pf[b, s], DT, c['m'], c['g'], c['J'], c['rh'])
             assert np.abs(outs[2][b, s] - Xr).max() <= 1e-12
         assert np.abs(outs[1][b] - pl.convert(Xr)).max() <= 1e-12
-    got = gpu_grads(ctx_for('3f', 10), X0, U, pf, n, g, cots, c, layout, want=('X0', 'U', 'pf') if n else ('X0', 'U'))
+    got = gpu_grads(ctx_for('3f', 10, cset), X0, U, pf, n, g, cots, c, layout, want=('X0', 'U', 'pf') if n else ('X0', 'U'))
     d = {k: figure(v, ref[k]) for k, v in got.items()}
     print(f'PVJP1 n={n} B={B} {cots} {layout} ' + ' '.join(f'{k}={v:.3e} (max {np.abs(ref[k]).max():.2e})'
                                                         for k, v in d.items()))

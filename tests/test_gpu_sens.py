@@ -27,16 +27,16 @@ max(10 x its class's GPU figure, the two routes' disagreement in that case):
   e2e       1.241e-11    2.212e-09   (solve_device fp64, then sens_device)
 """
 import functools
-import os
 
 import numpy as np
 import pytest
 
 torch = pytest.importorskip('torch')
 
+from test_gpu_kkt import ctx_for as kkt_ctx_for, mpc_params, windows   # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(__file__), 'golden')
 TOL = {'noz': 1.5e-9, 'z2': 1.8e-10, 'ride': 1.25e-10, 'e2e': 1.25e-10}   # 10 x the class's GPU figure
 IDX = {'3f': (0, 5, 8), '2f': (0, 7, 15)}   # golden windows the oracle solves in every mode used
 CASES = [(v, N, IDX[v], 'drop') for v in ('3f', '2f') for N in (1, 2, 3, 10)]
@@ -48,14 +48,8 @@ CASES += [('3f', 2, IDX['3f'], 'stage1'), ('2f', 10, IDX['2f'], 'stage1')]
 IDS = ['-'.join(map(str, (c[0], c[1], len(c[2]), c[3]))) for c in CASES]
 
 
-def ctx_for(variant, N):
-    import hmpc
-    from oracle import hmpc_oracle as ho
-    if not torch.cuda.is_available():
-        pytest.fail('GPU tests need an MI355X (torch.cuda.is_available() is False)')
-    c = ho.runner_constants()
-    return hmpc.Context(variant, N, t=c['t'], m=c['m'], g=c['g'], mu=1.0, Jinv=c['Jinv'], rh=c['rh'],
-                        uref_mode='per_stage')
+def ctx_for(variant, N, consts=None):
+    return kkt_ctx_for(variant, N, 'per_stage', consts)
 
 
 def dense_sens(qp, N, z, skip, route, tol=1e-8):
@@ -83,22 +77,18 @@ def dense_sens(qp, N, z, skip, route, tol=1e-8):
 
 
 @functools.lru_cache(maxsize=None)
-def reference(variant, N, idx, mode):
+def reference(variant, N, idx, mode, consts=None):
     """Inputs [B, ...], the oracle's primal, S by both routes, the instances
     expected singular and the z-row counts (computed once, shared)."""
-    import hmpc_plan
     from oracle import hmpc_oracle as ho
-    if N == 64:
-        d = hmpc_plan.sample_instances(max(idx) + 1, N, curve=True, seed=64)
-    else:
-        d = np.load(os.path.join(GOLDEN, f'qp_{variant}_N10_straight.npz'))
-    inst = {k: np.array(d[k][list(idx)], dtype=np.float64) for k in ('x_in', 'x_lin', 'x_ref', 'pf', 'C', 'mu')}
+    inst = windows(variant, N, idx)
     inst['x_lin'] = inst['x_lin'][:, :N + 1]
     for k in ('x_ref', 'pf', 'C'):
         inst[k] = np.ascontiguousarray(inst[k][:, :N])
     if mode == 'mu':
         inst['mu'][:] = (0.5, 0.7, 0.9)
-    z0, vz, zref = {'plain': (None,) * 3, 'mu': (None,) * 3, 'drop': (0.14, -1.0, 0.05), 'zref': (None, None, 0.05),
+    z0, vz, zref = {'plain': (None,) * 3, 'mu': (None,) * 3, 'drop': (0.14, -1.0, 0.05), 'drop6': (0.14, -0.6, 0.05),
+                    'zref': (None, None, 0.05),
                     'ride': (0.104, -0.1, -2.0), 'stage1': (0.102, -0.1, 0.05)}[mode]
     if z0 is not None:
         inst['x_in'][:, 2], inst['x_in'][:, 8] = z0, vz
@@ -109,7 +99,7 @@ def reference(variant, N, idx, mode):
     inst['x_lin'][:, 0] = inst['x_in']
     ref = dict(u=[], x=[], S=[], S2=[])
     for i in range(len(idx)):
-        p = ho.MpcParams.runner(variant, N, mu=float(inst['mu'][i]))
+        p = mpc_params(variant, N, float(inst['mu'][i]), consts)
         s = ho.solve_instance(p, inst['x_in'][i], inst['x_lin'][i], inst['x_ref'][i], inst['pf'][i],
                               inst['C'][i], 'per_stage')
         assert s['status'] == 'solved', (variant, N, idx[i], mode)
@@ -165,9 +155,9 @@ def test_inputs_cover_the_classes():
 
 
 @pytest.mark.parametrize('variant,N,idx,mode', CASES, ids=IDS)
-def test_jacobian_at_the_exact_primal(variant, N, idx, mode):
-    inst, ref = reference(variant, N, idx, mode)
-    ctx = ctx_for(variant, N)
+def test_jacobian_at_the_exact_primal(variant, N, idx, mode, consts=None):
+    inst, ref = reference(variant, N, idx, mode, consts)
+    ctx = ctx_for(variant, N, consts)
     S, flags = run_sens(ctx, inst, ref['u'], ref['x'])
     S1, flags1 = run_sens(ctx, inst, ref['u'], ref['x'], n_stages=1)
     assert S.shape == (len(idx), N, 6, 12) and S1.shape == (len(idx), 1, 6, 12)

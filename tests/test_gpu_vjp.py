@@ -17,16 +17,16 @@ max(10 x its class's GPU figure, the two routes' disagreement in that case):
   ride      4.373e-10    2.121e-09   (N = 64, up to 19 z rows; worst: 3f)
 """
 import functools
-import os
 
 import numpy as np
 import pytest
 
 torch = pytest.importorskip('torch')
 
+from test_gpu_kkt import ctx_for as kkt_ctx_for, mpc_params, windows   # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(__file__), 'golden')
 TOL = {'noz': 1.434e-9, 'z2': 4.586e-10, 'ride': 4.373e-9}   # 10 x the class's GPU figure
 IDX = {'3f': (0, 5, 8), '2f': (0, 7, 15)}   # golden windows the oracle solves in every mode used
 CASES = [(v, N, IDX[v], 'drop') for v in ('3f', '2f') for N in (1, 2, 3, 10)]
@@ -36,18 +36,12 @@ CASES += [(v, 64, (4, 6, 7), 'ride') for v in ('3f', '2f')]
 CASES += [('3f', 2, IDX['3f'], 'stage1')]
 IDS = ['-'.join(map(str, (c[0], c[1], c[3]))) for c in CASES]
 OUTS = ('x_in', 'x_ref', 'pf')
-MODES = {'plain': (None,) * 3, 'mu': (None,) * 3, 'drop': (0.14, -1.0, 0.05), 'ride': (0.104, -0.1, -2.0),
+MODES = {'plain': (None,) * 3, 'mu': (None,) * 3, 'drop': (0.14, -1.0, 0.05), 'drop6': (0.14, -0.6, 0.05), 'ride': (0.104, -0.1, -2.0),
          'stage1': (0.102, -0.1, 0.05)}   # x_in z, vz and the z reference
 
 
-def ctx_for(variant, N):
-    import hmpc
-    from oracle import hmpc_oracle as ho
-    if not torch.cuda.is_available():
-        pytest.fail('GPU tests need an MI355X (torch.cuda.is_available() is False)')
-    c = ho.runner_constants()
-    return hmpc.Context(variant, N, t=c['t'], m=c['m'], g=c['g'], mu=1.0, Jinv=c['Jinv'], rh=c['rh'],
-                        uref_mode='per_stage')
+def ctx_for(variant, N, consts=None):
+    return kkt_ctx_for(variant, N, 'per_stage', consts)
 
 
 def dense_jac(qp, N, z, skip, dB, route, tol=1e-8):
@@ -87,16 +81,11 @@ def split(grad, N):
 
 
 @functools.lru_cache(maxsize=None)
-def reference(variant, N, idx, mode):
+def reference(variant, N, idx, mode, consts=None):
     """Inputs [B, ...], the oracle's primal, the cotangents, the gradients by both routes for
     (g_u, g_x), (g_u, 0) and (0, g_x), the instances expected singular and the z-row counts."""
-    import hmpc_plan
     from oracle import hmpc_oracle as ho
-    if N == 64:
-        d = hmpc_plan.sample_instances(max(idx) + 1, N, curve=True, seed=64)
-    else:
-        d = np.load(os.path.join(GOLDEN, f'qp_{variant}_N10_straight.npz'))
-    inst = {k: np.array(d[k][list(idx)], dtype=np.float64) for k in ('x_in', 'x_lin', 'x_ref', 'pf', 'C', 'mu')}
+    inst = windows(variant, N, idx)
     inst['x_lin'] = inst['x_lin'][:, :N + 1]
     for k in ('x_ref', 'pf', 'C'):
         inst[k] = np.ascontiguousarray(inst[k][:, :N])
@@ -112,7 +101,7 @@ def reference(variant, N, idx, mode):
     rng = np.random.default_rng(len(idx) * 1000 + N)
     ref = dict(u=[], x=[], g_u=rng.standard_normal((len(idx), N, 6)), g_x=rng.standard_normal((len(idx), N + 1, 12)))
     for i in range(len(idx)):
-        p = ho.MpcParams.runner(variant, N, mu=float(inst['mu'][i]))
+        p = mpc_params(variant, N, float(inst['mu'][i]), consts)
         s = ho.solve_instance(p, inst['x_in'][i], inst['x_lin'][i], inst['x_ref'][i], inst['pf'][i],
                               inst['C'][i], 'per_stage')
         assert s['status'] == 'solved', (variant, N, idx[i], mode)
@@ -158,9 +147,9 @@ def bound(ref, key='full'):
 
 
 @pytest.mark.parametrize('variant,N,idx,mode', CASES, ids=IDS)
-def test_gradients_at_the_exact_primal(variant, N, idx, mode):
-    inst, ref = reference(variant, N, idx, mode)
-    got = run_vjp(ctx_for(variant, N), inst, ref)
+def test_gradients_at_the_exact_primal(variant, N, idx, mode, consts=None):
+    inst, ref = reference(variant, N, idx, mode, consts)
+    got = run_vjp(ctx_for(variant, N, consts), inst, ref)
     assert got['x_in'].shape == (len(idx), 12) and got['x_ref'].shape == (len(idx), N, 12)
     assert got['pf'].shape == (len(idx), N, 3)
     assert np.array_equal(got['flags'] != 0, ref['singular'])   # stage1: exactly the predicted instances

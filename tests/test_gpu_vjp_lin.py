@@ -26,6 +26,7 @@ import pytest
 
 torch = pytest.importorskip('torch')
 
+from test_gpu_kkt import mpc_params   # noqa: E402
 from test_gpu_vjp import CASES, IDS, IDX, TOL, ctx_for, reference as vjp_reference   # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -72,10 +73,10 @@ def dense_jac_lin(qp, N, z, act, dAd, dBd, dA_mu, route):
     return np.linalg.lstsq(kkt, np.vstack([-c, D]), rcond=1e-13)[0][:nz]
 
 
-def instance_jac(variant, N, inst, i, x, u, route, x_lin=None):
+def instance_jac(variant, N, inst, i, x, u, route, x_lin=None, consts=None):
     """(J [nz, 4 N + 13], the number of held friction rows) of instance i at the primal (x, u)"""
     from oracle import hmpc_oracle as ho
-    p = ho.MpcParams.runner(variant, N, mu=float(inst['mu'][i]))
+    p = mpc_params(variant, N, float(inst['mu'][i]), consts)
     Gd = ho.constant_matrices(p)[2]
     dyn = lambda xl: ho.gen_dt_dynamics(p, xl, inst['pf'][i])   # noqa: E731
     qp_of = lambda q, AB: ho.build_qp(q, inst['x_in'][i], inst['x_ref'][i], *AB, Gd, inst['C'][i], 'per_stage')   # noqa: E731
@@ -96,20 +97,20 @@ def instance_jac(variant, N, inst, i, x, u, route, x_lin=None):
             d = [(a - 8 * b + 8 * c - dd) / (12 * H) for a, b, c, dd in zip(m2, m1, p1, p2)]
         dAd.append(d[0])
         dBd.append(d[1])
-    dA_mu = qp_of(ho.MpcParams.runner(variant, N, mu=float(inst['mu'][i]) + 1.0), AB)['A'] - qp['A']
+    dA_mu = qp_of(mpc_params(variant, N, float(inst['mu'][i]) + 1.0, consts), AB)['A'] - qp['A']
     return dense_jac_lin(qp, N, z, act, dAd, dBd, dA_mu, route), int(np.any(dA_mu[act] != 0, axis=1).sum())
 
 
 @functools.lru_cache(maxsize=None)
-def reference(variant, N, idx, mode):
+def reference(variant, N, idx, mode, consts=None):
     """test_gpu_vjp's inputs, primal and cotangents, plus (route) -> per-instance dicts of the
     reference grad_x_lin [N+1,12] and grad_mu, and the per-instance count of held friction rows."""
-    inst, ref = vjp_reference(variant, N, idx, mode)
+    inst, ref = vjp_reference(variant, N, idx, mode, consts)
     lin = dict(fric=[])
     for i in range(len(idx)):
         g = np.concatenate([ref['g_x'][i].ravel(), ref['g_u'][i].ravel()])
         for route in ('svd', 'kkt'):
-            J, nf = instance_jac(variant, N, inst, i, ref['x'][i], ref['u'][i], route)
+            J, nf = instance_jac(variant, N, inst, i, ref['x'][i], ref['u'][i], route, consts=consts)
             grad, gl = J.T @ g, np.zeros((N + 1, 12))
             gl[:N, COLS] = grad[:4 * N].reshape(N, 4)
             lin.setdefault(route, []).append(dict(x_lin=gl, mu=grad[4 * N:4 * N + 1]))
@@ -146,9 +147,9 @@ def run(ctx, inst, ref, reps=1, fn='vjp_lin_device', **kw):
 
 
 @pytest.mark.parametrize('variant,N,idx,mode', CASES, ids=IDS)
-def test_gradients_at_the_exact_primal(variant, N, idx, mode):
-    inst, ref, lin = reference(variant, N, idx, mode)
-    ctx = ctx_for(variant, N)
+def test_gradients_at_the_exact_primal(variant, N, idx, mode, consts=None):
+    inst, ref, lin = reference(variant, N, idx, mode, consts)
+    ctx = ctx_for(variant, N, consts)
     got, old = run(ctx, inst, ref), run(ctx, inst, ref, fn='vjp_device')
     assert all(np.array_equal(got[o], old[o]) for o in ('x_in', 'x_ref', 'pf', 'flags'))   # bit for bit
     assert np.array_equal(got['flags'] != 0, ref['singular'])
@@ -175,17 +176,17 @@ def test_partial_outputs_multipliers_and_the_launch_grid():
     assert all(np.array_equal(big[o][-3:], big[o][:3]) and np.array_equal(big[o][:3], full[o]) for o in full)
 
 
-def mpcontrol_chain(variant, N, inst, i, g_u):
+def mpcontrol_chain(variant, N, inst, i, g_u, consts=None):
     """Dense chain rule through Mpc.mpcontrol for the loss sum(g_u u): d/d x_in of the init call,
     d/d x_prev of a non-init call on x_prev = the init call's first solution; and that x_prev."""
     from oracle import hmpc_oracle as ho
-    p = ho.MpcParams.runner(variant, N, mu=float(inst['mu'][i]))
+    p = mpc_params(variant, N, float(inst['mu'][i]), consts)
     g = np.concatenate([np.zeros((N + 1) * 12), g_u.ravel()])
 
     def back(x_lin, g):   # the solve at x_lin: its x*, grad_x_lin [N+1,12] and grad_x_in of the cotangent g
         s = ho.solve_instance(p, inst['x_in'][i], x_lin, inst['x_ref'][i], inst['pf'][i], inst['C'][i], 'per_stage')
         assert s['status'] == 'solved'
-        t = instance_jac(variant, N, inst, i, s['x'], s['u'], 'svd', x_lin=x_lin)[0].T @ g
+        t = instance_jac(variant, N, inst, i, s['x'], s['u'], 'svd', x_lin=x_lin, consts=consts)[0].T @ g
         gl = np.zeros((N + 1, 12))
         gl[:N, COLS] = t[:4 * N].reshape(N, 4)
         return s['x'], gl, t[4 * N + 1:]
